@@ -1,6 +1,15 @@
 """Benchmark of the MI355X MLSWE time-step engine (h-NUMO ti_rk_bcl hot path).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config dg25L3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config dg25L3] [--full] [--dump-outputs DIR]
+
+A plain N=1 run sets up, warms up, times the K steps and prints the result line (value,
+ms_per_step; "roofline" is null).  --full adds everything that takes runs of its own: the stage
+kernel's duration and the roofline figures made from it, the per-kernel step breakdown, the stream
+copy, the c4/c3/c5_single_gpu lines and the CPU baselines below.  --dump-outputs DIR writes the
+state the timed steps left (q_df, qb_df, qprime_df: what a caller of ti_rk_bcl receives after the
+last timed step) as DIR/<name>.npy in float64, at most 64 MB in all (a larger state: a seeded
+sample of each array, the same elements every run); the inputs are analytic, so two builds run
+with the same arguments can be compared output for output.
 
 One "step" is one baroclinic time step ti_rk_bcl (ti_rk_bcl.F90:9-87): two barotropic
 SSP(5,3) sub-cycles of N_btp*kstages stages each plus the layer predictor-corrector,
@@ -11,7 +20,7 @@ condition (data: synthetic IC, no files).
 
 Workloads (BASELINE.json configs):
   N=1   dg25L3  -- configs[1], the double gyre at 25x25 elements, N=4, 3 layers (the metric's
-                   1-GPU configuration); the line also carries "c4_single_gpu", the C4 mesh
+                   1-GPU configuration); with --full the line also carries "c4_single_gpu", the C4 mesh
                    below on this one GPU (the strong-scaling base of the N>1 lines), and
                    "c3_single_gpu", configs[2] (dg25N7L3: N=7, 3 layers, 25x25 elements), and
                    "c5_single_gpu", configs[4]'s mesh (lake200: the lake at rest, 2 layers) on this GPU.
@@ -277,6 +286,31 @@ def _limiter(frac: float, dram_frac: float | None, E: int) -> str:
     return f"not HBM: DRAM traffic at {dram_frac:.1%} of peak while the algorithmic bytes run at {frac:.1%}; {why}"
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000   # of values: the files stay below 64 MB with their headers
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname: str, arrays: dict, suffix: str = "") -> dict:
+    """Write the timed path's outputs as <dirname>/<name><suffix>.npy (float64).  Within
+    DUMP_LIMIT_BYTES in all the arrays are written whole, in their own shape; a larger state is
+    written as a 1-D sample of each array (of its elements in Fortran order), drawn with the fixed
+    seed DUMP_SEED from the array's size alone -- the same elements in every run and every build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.size * 8 for a in arrays.values())
+    rng = np.random.default_rng(DUMP_SEED)
+    info = {}
+    for name in sorted(arrays):
+        a = np.asarray(arrays[name], dtype=np.float64)
+        if total > DUMP_LIMIT_BYTES:
+            n = max(1, int(a.size * (DUMP_LIMIT_BYTES / total)))
+            idx = np.sort(rng.choice(a.size, size=n, replace=False))
+            a = a.ravel(order="F")[idx]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+        info[name + suffix] = {"shape": list(a.shape), "sampled": total > DUMP_LIMIT_BYTES}
+    return info
+
+
 def _claim_stdout():
     """The JSON line is the only thing on stdout: libraries that print to fd 1 (RCCL's version
     banner at communicator set-up, the HIP runtime) are sent to stderr; the line goes to a private
@@ -307,6 +341,13 @@ def main():
                     help="--emulate: what the rank's processor faces receive -- its own traces (mirror; default "
                          "except lake configs) or the first message of each exchange site again (frozen: the "
                          "at-rest neighbour of an at-rest lake; hnumo_debug_frozen_halo)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also the measurements that take runs of their own -- the stage kernel's roofline, the "
+                         "per-kernel step breakdown, the stream copy, the c4/c3/c5_single_gpu lines and the CPU "
+                         "baselines (off: the timed steps alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the state after the last timed step as DIR/<name>.npy (float64; at most 64 MB in all, "
+                         "a seeded sample of a larger state)")
     ap.add_argument("--cpu-steps", type=int, default=8)
     ap.add_argument("--cpu-cores", type=int, default=16,
                     help="MPI ranks (= host cores) of the reference CPU baseline (the GPU box's share is 16)")
@@ -466,14 +507,20 @@ def main():
     path = timed_path
     kname = "btp_subcycle_kernel" if path == "persistent" else "btp_stage_kernel"
     k_src = "graph event nodes around the corrector sub-cycle"
-    if not (k_ms and k_ms > 0):
+    eng.sync(q, qb, qp)
+    if not (abs(qb).max() < 1e30):
+        raise RuntimeError("non-finite state after benchmark")
+    dumped = None
+    if args.dump_outputs:
+        # the state the timed steps left, before any diagnostic run below advances it
+        dumped = dump_outputs(args.dump_outputs, {"q_df": q, "qb_df": qb, "qprime_df": qp},
+                              f".rank{rank}" if world > 1 else "")
+    if not (k_ms and k_ms > 0) and (multi or args.full):
+        # (a run of its own: at N=1 only with --full; without it the line carries no roofline)
         k_ms = eng.time_stage_kernel(2)
         k_src = "events around 2 direct corrector sub-cycles" + (" (incl. halo exchanges)" if multi else "")
     if path == "persistent":
         k_src += "; one launch per sub-cycle, time per stage = launch time / (N_btp*kstages)"
-    eng.sync(q, qb, qp)
-    if not (abs(qb).max() < 1e30):
-        raise RuntimeError("non-finite state after benchmark")
     halo_check = None
     if live_halo:
         # the halo proves itself: one step from the IC over the live RCCL transport against the
@@ -517,7 +564,7 @@ def main():
     roof = None
     bd = None
     copy_bw = None
-    if not multi:
+    if not multi and args.full:
         bd = step_breakdown(eng, case, 2)
         copy_bw = stream_copy(local_rank)
     if k_ms and k_ms > 0:
@@ -573,6 +620,8 @@ def main():
     # every HNUMO_* environment setting the engine read (hnumo_overrides; experiment knobs are
     # honoured only with HNUMO_EXPERIMENTS=1): empty on a clean box
     out["engine_env"] = eng.overrides
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     eng.close()
     if multi and not weak and not args.no_base:
         # the strong-scaling base: the whole mesh on rank 0's GPU alone, timed in this run, so the
@@ -609,7 +658,7 @@ def main():
                     "projection (xGMI transfer time of the real messages not included)"}
     if multi:
         out["setup_s"] = setup
-    if rank == 0 and not multi and not args.no_c4 and args.config is None:
+    if rank == 0 and not multi and args.full and not args.no_c4 and args.config is None:
         for key, cfg, wl, n in [("c4_single_gpu", "dg316L3", "dg316L3 (C4: 316x316 elements, N=4, 3 layers)", 3),
                                 ("c3_single_gpu", "dg25N7L3", "dg25N7L3 (C3: 25x25 elements, N=7, 3 layers)", 5),
                                 ("c5_single_gpu", "lake200", "lake200 (C5: the lake at rest, 200x200 elements, "
@@ -625,7 +674,7 @@ def main():
                 del c
             except Exception as exc:  # pragma: no cover - diagnostic only
                 out[key] = {"error": f"{type(exc).__name__}: {exc}"}
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if rank == 0 and not multi and args.full and not args.no_cpu_baseline:
         ncores = max(1, min(args.cpu_cores, len(os.sched_getaffinity(0))))
         out["cpu_baseline"] = cpu_baseline(build_case(make_config(cfg_name)), args.cpu_steps, ncores)
     if rank == 0:

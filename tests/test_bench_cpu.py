@@ -74,5 +74,29 @@ def test_self_neighbour_mirrors_the_processor_faces_statics():
 def test_bench_cli_lists_the_emulation_and_baseline_switches():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
                          check=True).stdout
-    for flag in ("--emulate", "--emulate-lists", "--order", "--no-base", "--no-c4-cpu"):
+    for flag in ("--emulate", "--emulate-lists", "--order", "--no-base", "--no-c4-cpu", "--full", "--dump-outputs"):
         assert flag in out
+
+
+def test_dump_outputs_writes_whole_arrays_or_the_same_seeded_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: float64 .npy files; within the limit the arrays whole and in their own
+    shape, above it a sample of each array within the limit, the same elements on every call."""
+    import bench
+    a = {"q_df": np.arange(90.0).reshape((3, 10, 3), order="F"), "qb_df": np.asfortranarray(np.ones((4, 10)))}
+    info = bench.dump_outputs(str(tmp_path / "whole"), a)
+    assert info["q_df"] == {"shape": [3, 10, 3], "sampled": False}
+    assert np.array_equal(np.load(tmp_path / "whole" / "q_df.npy"), a["q_df"])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 400)   # 130 values of 8 bytes do not fit
+    info = bench.dump_outputs(str(tmp_path / "s1"), a)
+    bench.dump_outputs(str(tmp_path / "s2"), {k: v.copy(order="F") for k, v in a.items()})
+    size = 0
+    for k in a:
+        x, y = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")
+        assert x.dtype == np.float64 and x.ndim == 1 and info[k]["sampled"] and np.array_equal(x, y)
+        assert np.isin(x, a[k]).all()
+        size += x.nbytes
+    assert 0 < size <= 400
+    # the q_df sample is a strictly increasing pick of its Fortran-order elements
+    flat = a["q_df"].ravel(order="F")
+    pos = np.searchsorted(flat, np.load(tmp_path / "s1" / "q_df.npy"))
+    assert (np.diff(pos) > 0).all()

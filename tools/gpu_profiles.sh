@@ -20,7 +20,7 @@ for cfg in $CFGS; do
     dg25N7L3) S=10; W=2 ;;
     *) S=20; W=3 ;;
   esac
-  B="python3 bench.py --config $cfg --no-cpu-baseline --no-c4"
+  B="python3 bench.py --full --config $cfg --no-cpu-baseline --no-c4"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt_$cfg -o run --output-format csv -- $B --steps $S --warmup $W > $O/kt_$cfg.log 2>&1 || { echo "kt $cfg failed"; tail -20 $O/kt_$cfg.log; exit 1; }
   tail -1 $O/kt_$cfg.log
   for c in FETCH_SIZE WRITE_SIZE; do

@@ -8,8 +8,8 @@
 #   tests        pytest -m gpu (the whole GPU suite)
 #   test:<expr>  pytest -m gpu -k <expr>
 #   smoke        __graft_entry__.smoke()
-#   bench        the default bench line (N=1: dg25L3 + C4 + C3 + CPU baselines)
-#   benchq       the bench line without the CPU baselines
+#   bench        the full bench line (bench.py --full, N=1: dg25L3 + C4 + C3 + C5 + CPU baselines)
+#   benchq       the full bench line without the CPU baselines
 #   emu8         bench.py --emulate 8:1 (C4 rank 1 of 8) under torch.distributed.run, one process
 #   emu4lake     bench.py --emulate 4:1 --config lake200 (C5 rank 1 of 4) the same way
 #   nb56         tools/ab_env.py: C4 per-stage kernel, LEAN arena for 5 vs 6 workgroups per CU
@@ -47,10 +47,10 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail "$step" $? $O/smoke.log
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err || fail "$step" $? $O/bench.err
+      timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err || fail "$step" $? $O/bench.err
       cat $O/bench.json ;;
     benchq)
-      timeout -k 10 600 python bench.py --no-cpu-baseline > $O/benchq.json 2> $O/benchq.err || fail "$step" $? $O/benchq.err
+      timeout -k 10 600 python bench.py --full --no-cpu-baseline > $O/benchq.json 2> $O/benchq.err || fail "$step" $? $O/benchq.err
       cat $O/benchq.json ;;
     emu8)
       timeout -k 10 600 $TR bench.py --emulate 8:1 > $O/emu8.json 2> $O/emu8.err || fail "$step" $? $O/emu8.err
@@ -59,7 +59,7 @@ for step in "$@"; do
       timeout -k 10 600 $TR bench.py --emulate 4:1 --config lake200 > $O/emu4lake.json 2> $O/emu4lake.err || fail "$step" $? $O/emu4lake.err
       cat $O/emu4lake.json ;;
     lake1)
-      timeout -k 10 600 python bench.py --config lake200 --no-cpu-baseline --steps 10 > $O/lake1.json 2> $O/lake1.err || fail "$step" $? $O/lake1.err
+      timeout -k 10 600 python bench.py --full --config lake200 --no-cpu-baseline --steps 10 > $O/lake1.json 2> $O/lake1.err || fail "$step" $? $O/lake1.err
       cat $O/lake1.json ;;
     emu4lake2)
       timeout -k 10 600 $TR bench.py --emulate 4:1 --config lake200 --warmup 1 --steps 2 > $O/emu4lake2.json 2> $O/emu4lake2.err || fail "$step" $? $O/emu4lake2.err
