@@ -3,7 +3,9 @@
 // The engine owns all device state and reproduces the call sequence of ti_rk_bcl
 // (ti_rk_bcl.F90:9-87) with the kernels of kernels_btp.hip / kernels_bcl.hip.  A whole
 // baroclinic step (2 barotropic sub-cycles = 2*N_btp*kstages fused stage kernels plus
-// ~20 baroclinic kernels) is captured once into a hipGraph and replayed.
+// ~20 baroclinic kernels) is captured once into a hipGraph and replayed.  The run diagnostics of
+// the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) are plain
+// launches on the same stream between replays.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -24,6 +26,7 @@
 #include "kernels_bcl.hip"
 #include "kernels_btp.hip"
 #include "kernels_lapq.hip"
+#include "kernels_diag.hip"
 
 using namespace hnumo;
 
@@ -175,6 +178,16 @@ struct hnumo_engine {
     std::vector<const char *> name;
     size_t n = 0;
   } *km = nullptr;
+  // on-device run diagnostics (kernels_diag.hip).  has_state: q and qb were uploaded at least once;
+  // the rest is hnumo_diag_geometry's: the running cell minima of courant.F90:98-99 per sub-cell
+  // of the diag_ne elements that count, their final values, the mass weights (the caller's
+  // wjac_df, or the nodal jac of the statics), the workgroups' partial results and the out array
+  bool has_state = false, diag_geom = false;
+  int diag_ne = 0, diag_nb = 0;
+  double *diag_cdx = nullptr, *diag_cdy = nullptr, *diag_wjac = nullptr, *diag_part = nullptr, *diag_out = nullptr;
+  const double *diag_w = nullptr;
+  double *h_diag = nullptr;                  // pinned copy of diag_out
+  double diag_min_dx = 1e16, diag_min_dy = 1e16;
 };
 
 // the per-kernel breakdown's mark after a launch on the engine stream (no-op outside
@@ -1013,12 +1026,22 @@ extern "C" {
 
 int hnumo_abi_version(void) { return HNUMO_ABI_VERSION; }
 
+static int fail(hnumo_engine *eng, int code, const std::string &msg) {
+  eng->err = msg;
+  return code;
+}
+
 int hnumo_overrides(const hnumo_engine *eng, char *out, int64_t len) {
-  if (!eng || !out || len <= 0) return HNUMO_ERR_INVALID;
+  if (!eng) return HNUMO_ERR_INVALID;
+  hnumo_engine *e = const_cast<hnumo_engine *>(eng);  // (the message is not part of the engine's state)
+  if (!out || len <= 0) return fail(e, HNUMO_ERR_INVALID, "hnumo_overrides: no output buffer");
   const size_t n = std::min((size_t)len - 1, eng->overrides.size());
   std::memcpy(out, eng->overrides.data(), n);
   out[n] = 0;
-  return eng->overrides.size() < (size_t)len ? HNUMO_OK : HNUMO_ERR_INVALID;
+  if (eng->overrides.size() >= (size_t)len)
+    return fail(e, HNUMO_ERR_INVALID, "hnumo_overrides: " + std::to_string(len) + " bytes are too few for the " +
+                                          std::to_string(eng->overrides.size() + 1) + " of the text (cut)");
+  return HNUMO_OK;
 }
 
 const char *hnumo_last_error(const hnumo_engine *eng) { return eng ? eng->err.c_str() : "null engine"; }
@@ -1031,6 +1054,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   for (void *ptr : eng->allocs) (void)hipFree(ptr);
   if (eng->h_neg) (void)hipHostFree(eng->h_neg);
   if (eng->h_steps) (void)hipHostFree(eng->h_steps);
+  if (eng->h_diag) (void)hipHostFree(eng->h_diag);
   if (eng->stream && eng->own_stream) (void)hipStreamDestroy(eng->stream);
   if (LocalGroup *g = eng->group) {
     // the destroyed engine cannot take part in exchanges any more; the last one out frees
@@ -1058,11 +1082,6 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
     if (ev) (void)hipEventDestroy(ev);
   if (eng->stream2) (void)hipStreamDestroy(eng->stream2);
   delete eng;
-}
-
-static int fail(hnumo_engine *eng, int code, const std::string &msg) {
-  eng->err = msg;
-  return code;
 }
 
 int hnumo_engine_create(const hnumo_mesh_desc *mesh, const hnumo_static_desc *st, const hnumo_params *par,
@@ -1685,6 +1704,7 @@ static int upload_state(hnumo_engine *eng, const double *q, const double *qb, co
   if (qb) HIPCHK(hipMemcpyAsync(eng->qb, qb, 4 * (size_t)eng->npoin * 8, hipMemcpyHostToDevice, eng->stream));
   if (qp) HIPCHK(hipMemcpyAsync(eng->qp, qp, n3 * 8, hipMemcpyHostToDevice, eng->stream));
   if (qp && fused_extract(eng)) DISPATCH(eng, extract(eng, eng->qp, eng->qf, 0));
+  if (q && qb) eng->has_state = true;
   return 0;
 }
 
@@ -1957,6 +1977,148 @@ int hnumo_sync(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime_df
   if (!eng) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   return download_state(eng, q_df, qb_df, qprime_df);
+}
+
+// ------------------------------------------------------------------ on-device run diagnostics
+// (kernels_diag.hip; plain launches on the engine stream, outside the captured step)
+static DiagArgs diag_args(const hnumo_engine *eng) {
+  DiagArgs a{};
+  a.q = eng->q;
+  a.qb = eng->qb;
+  a.zbot = eng->nstat + (size_t)NS_ZB * eng->npoin;
+  a.alpha = eng->alpha;
+  a.cdx = eng->diag_cdx;
+  a.cdy = eng->diag_cdy;
+  a.gravity = eng->p.gravity;
+  a.dt = eng->p.dt;
+  a.dt_btp = eng->p.dt_btp;
+  a.npoin = eng->npoin;
+  a.ne = eng->diag_ne;
+  a.ngl = eng->ngl;
+  return a;
+}
+
+int hnumo_diag_geometry(hnumo_engine *eng, const double *coord, int32_t ldc, const double *wjac_df) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!coord) return fail(eng, HNUMO_ERR_INVALID, "hnumo_diag_geometry: coord is NULL");
+  if (ldc != 2 && ldc != 3)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_diag_geometry: ldc must be 2 or 3 (coord(ldc,npoin)), got " + std::to_string(ldc));
+  if (eng->L < 1 || eng->L > MAXL || eng->ngl < 2 || eng->ngl * eng->ngl > DG_BS)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_diag_geometry: unsupported nlayers or ngl");
+  HIPCHK(hipSetDevice(eng->device));
+  // the owned elements of a ghost-layer partition, every local element otherwise: what each rank of
+  // the reference computes before its mpi_reduce
+  const int ne = eng->nelem_owned, ngl = eng->ngl, P = eng->P, nc = ngl - 1;
+  const size_t ncell = (size_t)ne * nc * nc;
+  // courant.F90:70-99: the running minima of dx = maxval(x) - minval(x) over the 4 corners, in the
+  // loop order ie, j, i
+  std::vector<double> cdx(ncell), cdy(ncell);
+  double min_dx = 1e16, min_dy = 1e16;
+  size_t c = 0;
+  for (int ie = 0; ie < ne; ie++)
+    for (int j = 0; j < nc; j++)
+      for (int i = 0; i < nc; i++, c++) {
+        const size_t n0 = (size_t)ie * P + (size_t)j * ngl + i;
+        const size_t nd[4] = {n0, n0 + 1, n0 + ngl, n0 + ngl + 1};
+        double xl = coord[ldc * nd[0]], xh = xl, yl = coord[ldc * nd[0] + 1], yh = yl;
+        for (int m = 1; m < 4; m++) {
+          const double x = coord[ldc * nd[m]], y = coord[ldc * nd[m] + 1];
+          xl = std::min(xl, x), xh = std::max(xh, x);
+          yl = std::min(yl, y), yh = std::max(yh, y);
+        }
+        min_dx = std::min(min_dx, xh - xl);
+        min_dy = std::min(min_dy, yh - yl);
+        cdx[c] = min_dx;
+        cdy[c] = min_dy;
+      }
+  if (!eng->diag_cdx) {
+    const int EPB = DG_BS / P;
+    eng->diag_nb = std::max(1, std::min((ne + EPB - 1) / EPB, 1024));
+    eng->diag_cdx = dalloc<double>(eng, ncell);
+    eng->diag_cdy = dalloc<double>(eng, ncell);
+    eng->diag_part = dalloc<double>(eng, (size_t)dg_nv(eng->L) * eng->diag_nb);
+    eng->diag_out = dalloc<double>(eng, dg_nout(eng->L));
+    if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hnumo_diag_geometry: device allocation failed");
+    HIPCHK(hipHostMalloc((void **)&eng->h_diag, dg_nout(eng->L) * sizeof(double)));
+  }
+  if (wjac_df && !eng->diag_wjac) {
+    eng->diag_wjac = dalloc<double>(eng, eng->npoin);
+    if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hnumo_diag_geometry: device allocation failed");
+  }
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a diagnostics launch in flight reads the old tables)
+  if (ncell) {
+    HIPCHK(hipMemcpy(eng->diag_cdx, cdx.data(), ncell * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(eng->diag_cdy, cdy.data(), ncell * 8, hipMemcpyHostToDevice));
+  }
+  if (wjac_df) HIPCHK(hipMemcpy(eng->diag_wjac, wjac_df, (size_t)eng->npoin * 8, hipMemcpyHostToDevice));
+  eng->diag_w = wjac_df ? eng->diag_wjac : eng->nstat + (size_t)NS_W * eng->npoin;
+  eng->diag_ne = ne;
+  eng->diag_min_dx = min_dx;
+  eng->diag_min_dy = min_dy;
+  eng->diag_geom = true;
+  return HNUMO_OK;
+}
+
+int hnumo_diagnostics(hnumo_engine *eng, int32_t flags, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_diagnostics: out is NULL");
+  if (eng->L < 1 || eng->L > MAXL) return fail(eng, HNUMO_ERR_INVALID, "hnumo_diagnostics: unsupported nlayers");
+  const int L = eng->L, nout = dg_nout(L);
+  if (n != nout)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_diagnostics: n must be 12 + 11*nlayers = " + std::to_string(nout) +
+                                            ", got " + std::to_string(n));
+  if (!eng->diag_geom) return fail(eng, HNUMO_ERR_INVALID, "hnumo_diagnostics: call hnumo_diag_geometry first");
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_diagnostics: no state on the device yet (run a step first)");
+  HIPCHK(hipSetDevice(eng->device));
+  const DiagArgs a = diag_args(eng);
+  const int nb = eng->diag_nb;
+  HIPCHK(hipMemsetAsync(eng->diag_out, 0, nout * sizeof(double), eng->stream));
+  switch (L) {
+    case 1: hipLaunchKernelGGL(diag_reduce_kernel<1>, dim3(nb), dim3(DG_BS), 0, eng->stream, a, eng->diag_part); break;
+    case 2: hipLaunchKernelGGL(diag_reduce_kernel<2>, dim3(nb), dim3(DG_BS), 0, eng->stream, a, eng->diag_part); break;
+    default: hipLaunchKernelGGL(diag_reduce_kernel<3>, dim3(nb), dim3(DG_BS), 0, eng->stream, a, eng->diag_part); break;
+  }
+  hipLaunchKernelGGL(diag_final_kernel, dim3(dg_nv(L)), dim3(64), 0, eng->stream, eng->diag_part, nb, L, eng->diag_out);
+  if (flags & 1)
+    hipLaunchKernelGGL(diag_mass_kernel, dim3(L), dim3(DG_BS), 0, eng->stream, eng->q, eng->diag_w, eng->alpha,
+                       eng->p.gravity, (size_t)eng->npoin, (size_t)eng->diag_ne * eng->P, eng->diag_out);
+  HIPCHK(hipMemcpyAsync(eng->h_diag, eng->diag_out, nout * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  std::memcpy(out, eng->h_diag, nout * sizeof(double));
+  out[2] = eng->diag_min_dx;
+  out[3] = eng->diag_min_dy;
+  return HNUMO_OK;
+}
+
+int hnumo_layer_fields(hnumo_engine *eng, double *out5, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!out5) return fail(eng, HNUMO_ERR_INVALID, "hnumo_layer_fields: out5 is NULL");
+  if (eng->L < 1 || eng->L > MAXL) return fail(eng, HNUMO_ERR_INVALID, "hnumo_layer_fields: unsupported nlayers");
+  const int64_t want = 5 * (int64_t)eng->npoin * eng->L;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_layer_fields: n must be 5*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_layer_fields: no state on the device yet (run a step first)");
+  HIPCHK(hipSetDevice(eng->device));
+  // (an output call, not a per-step one: the buffer lives for the call)
+  double *d = nullptr;
+  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
+  const DiagArgs a = diag_args(eng);
+  const int nb = (int)std::min<size_t>(((size_t)eng->npoin + DG_BS - 1) / DG_BS, 4096);
+  switch (eng->L) {
+    case 1: hipLaunchKernelGGL(diag_fields_kernel<1>, dim3(std::max(nb, 1)), dim3(DG_BS), 0, eng->stream, a, d); break;
+    case 2: hipLaunchKernelGGL(diag_fields_kernel<2>, dim3(std::max(nb, 1)), dim3(DG_BS), 0, eng->stream, a, d); break;
+    default: hipLaunchKernelGGL(diag_fields_kernel<3>, dim3(std::max(nb, 1)), dim3(DG_BS), 0, eng->stream, a, d); break;
+  }
+  hipError_t err = hipMemcpyAsync(out5, d, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(eng->stream);
+  if (err == hipSuccess) err = hipGetLastError();
+  (void)hipFree(d);
+  HIPCHK(err);
+  return HNUMO_OK;
 }
 
 int hnumo_btp_bcl_coeffs(hnumo_engine *eng, const double *qprime_df) {

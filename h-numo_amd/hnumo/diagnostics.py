@@ -9,10 +9,14 @@
     read_snapshot      mod_restart.F90:260-294        its reader (load_data_mlswe)
     restart_state      mod_restart.F90:15-87          q_df, qb_df, qprime_df from a snapshot
     time_loop          mod_time_loop.F90:61-269       the loop around ti_rk_bcl
+    format_diagnostics the text of print_diagnostics from ready values (the engine's on-device
+                       diagnostics, hnumo_diagnostics, or the host routines here)
     ci_check           CI/bump/check.F90:1-86         the reference CI's acceptance check
 
 All of it is host code on the state copied out of the engine (hnumo_sync); none of it is on
-the timed path.  Single rank: the reference's gathers (gather_data) are the identity.
+the timed path.  time_loop(device_diagnostics=True) takes the periodic reports' numbers from
+the engine instead (kernels_diag.hip: same bits, no sync).  Single rank: the reference's
+gathers (gather_data) are the identity.
 Fortran edit descriptors (Iw, Ew.d, ESw.d, Dw.d) are reproduced so that the files read like
 the reference's for the same state (tests/test_diagnostics.py).
 """
@@ -160,15 +164,30 @@ def print_diagnostics(case, qf, qb, time, itime, idone, mass0=None, time_scale=1
     """print_diagnostics_mlswe (print_diagnostics.F90:14-190) for the layer fields `qf`
     (layer_fields) and qb(4,npoin).  Returns (stdout text, mass_mlswe.cons line or None,
     mlswe_FIN.txt text or None).  mass0: the initial layer masses (lcheck_conserved)."""
+    mass = None
+    if mass0 is not None:
+        mass = [conserved_mass(case, qf[0, :, k]) for k in range(case.scalars["nlayers"])]
+    cfl_b, cfl, dxm, dym = courant(case, qf, qb)
+    return format_diagnostics(case, time, itime, idone, mass=mass, mass0=mass0, qmax=qf.max(axis=1),
+                              qmin=qf.min(axis=1), qbmax=qb.max(axis=1), qbmin=qb.min(axis=1), cfl_b=cfl_b,
+                              cfl=cfl, min_dx=dxm, min_dy=dym, time_scale=time_scale)
+
+
+def format_diagnostics(case, time, itime, idone, *, mass, mass0, qmax, qmin, qbmax, qbmin, cfl_b, cfl, min_dx,
+                       min_dy, time_scale=1.0):
+    """The text of print_diagnostics from ready values: the layer masses (None without
+    lcheck_conserved) and the initial ones, the extrema of the layer fields (5, nlayers) and of
+    qb (4), the Courant numbers and cell minima -- from the host routines above or from the
+    engine (hnumo.engine.Engine.diagnostics).  Returns what print_diagnostics returns."""
     S = case.scalars
     L = S["nlayers"]
-    mass, xm1 = None, [0.0] * L
+    xm1 = [0.0] * L
     if mass0 is not None:
-        mass = [conserved_mass(case, qf[0, :, k]) for k in range(L)]
+        mass = [float(m) for m in mass]
         xm1 = [abs(mass[k] - mass0[k]) / mass0[k] for k in range(L)]
-    qmax, qmin = qf.max(axis=1), qf.min(axis=1)
-    qbmax, qbmin = qb.max(axis=1), qb.min(axis=1)
-    cfl_b, cfl, dxm, dym = courant(case, qf, qb)
+    else:
+        mass = None
+    dxm, dym = min_dx, min_dy
     head = "itime time dt dt_btp = " + fmt_i(itime, 8) + " " + " ".join(
         fmt_es(v, 13, 5) for v in (time / time_scale, S["dt"], S["dt_btp"]))
     cfl_line = "CFL_B = " + fmt_e(cfl_b, 11, 4) + " CFL = " + fmt_e(cfl, 11, 4)
@@ -262,12 +281,19 @@ def restart_state(case, path):
 # ------------------------------------------------------------------ the time loop
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
-              time_scale=1.0, out=None):
+              time_scale=1.0, out=None, device_diagnostics=False):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
     out_dir; the stdout report goes to `out` (default sys.stdout).  Returns the final
-    (q_df, qb_df, qprime_df)."""
+    (q_df, qb_df, qprime_df).
+
+    device_diagnostics: with a stepper that has `diagnostics` (the engine), the reports after
+    steps take their numbers from stepper.diagnostics() -- computed on the device state, the same
+    bits -- instead of from the synced copy; without dump_data the final report does too, so no
+    sync is issued for reporting (the one before the return fills the returned arrays).  The
+    initial report and the initial masses stay on the host.  A stepper without `diagnostics`
+    reports on the host as with False."""
     S = case.scalars
     out = out or sys.stdout
     dt = S["dt"]
@@ -294,8 +320,17 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     if qout is None:
         qout = layer_fields(case, q)
 
-    def report(idone):
-        text, line, fin = print_diagnostics(case, qout, qb, time, itime, idone, mass0, time_scale)
+    on_device = bool(device_diagnostics) and hasattr(stepper, "diagnostics")
+
+    def report(idone, device=False):
+        if device:
+            d = stepper.diagnostics(mass=mass0 is not None)
+            text, line, fin = format_diagnostics(case, time, itime, idone, mass=d["mass"], mass0=mass0,
+                                                 qmax=d["qmax"], qmin=d["qmin"], qbmax=d["qbmax"],
+                                                 qbmin=d["qbmin"], cfl_b=d["cfl_b"], cfl=d["cfl"],
+                                                 min_dx=d["min_dx"], min_dy=d["min_dy"], time_scale=time_scale)
+        else:
+            text, line, fin = print_diagnostics(case, qout, qb, time, itime, idone, mass0, time_scale)
         out.write(text)
         if line is not None and cons is not None:
             cons.write(line + "\n")
@@ -308,10 +343,12 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     resident = hasattr(stepper, "set_resident")
     if resident:
         stepper.set_resident(True)
+    stepped = False
     while time < time_final:
         itime += 1
         time = time + dt
         stepper.ti_rk_bcl(q, qb, qp)
+        stepped = True
         if itime % irestart == 0 and dump_data:
             if resident:
                 stepper.sync(q, qb, qp)
@@ -319,12 +356,17 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
             write_snapshot(snap(inorm), case, q, qb)
             qout = layer_fields(case, q)
             if lprint_diagnostics:
-                report(0)
+                report(0, device=on_device)
+    final_on_device = on_device and not dump_data and stepped
+    if final_on_device:
+        report(1, device=True)
     if resident:
         stepper.sync(q, qb, qp)
     if cons is not None:
         cons.close()
         cons = None
+    if final_on_device:
+        return q, qb, qp
     if not dump_data:
         qout = layer_fields(case, q)
     report(1)

@@ -66,6 +66,9 @@ def lib():
         L.hnumo_step_breakdown.argtypes = [vp, C.c_int, C.c_char_p, C.c_int64, dp, C.c_int, C.POINTER(C.c_int)]
         L.hnumo_stream_copy_bw.argtypes = [C.c_int, C.c_int64, C.c_int, dp]
         L.hnumo_overrides.argtypes = [vp, C.c_char_p, C.c_int64]
+        L.hnumo_diag_geometry.argtypes = [vp, dp, C.c_int32, dp]
+        L.hnumo_diagnostics.argtypes = [vp, C.c_int32, dp, C.c_int64]
+        L.hnumo_layer_fields.argtypes = [vp, dp, C.c_int64]
         _lib = L
     return _lib
 
@@ -83,6 +86,20 @@ def _dp(a, size=None, name="array"):
 
 
 SUMMATION = {"reference": 0, "factored": 1}   # HNUMO_SUM_REFERENCE / HNUMO_SUM_FACTORED
+DIAG_MASS = 1                                 # HNUMO_DIAG_MASS
+
+
+def unpack_diagnostics(out, L: int) -> dict:
+    """hnumo_diagnostics' flat out array (12 + 11*L values: [cfl_b, cfl, min_dx, min_dy,
+    qbmax(4), qbmin(4)], then per layer [mass, qmax(5), qmin(5)]) as a dict; qmax/qmin are
+    (5, L) as print_diagnostics uses them, mass is (L,)."""
+    out = np.asarray(out, dtype=np.float64).reshape(-1)
+    if out.size != 12 + 11 * L:
+        raise ValueError(f"diagnostics: {out.size} values, expected 12 + 11*{L} = {12 + 11 * L}")
+    lay = out[12:].reshape(L, 11)
+    return {"cfl_b": float(out[0]), "cfl": float(out[1]), "min_dx": float(out[2]), "min_dy": float(out[3]),
+            "qbmax": out[4:8].copy(), "qbmin": out[8:12].copy(), "mass": lay[:, 0].copy(),
+            "qmax": np.ascontiguousarray(lay[:, 1:6].T), "qmin": np.ascontiguousarray(lay[:, 6:11].T)}
 
 
 class Engine:
@@ -111,6 +128,12 @@ class Engine:
             raise EngineError(rc, msg)
         if summation is not None:
             self.set_summation(summation)
+        if "coord" in case.arrays:
+            try:
+                self.diag_geometry(case.arrays["coord"], case.arrays.get("wjac_df"))
+            except EngineError:
+                self._destroy()
+                raise
 
     def _check(self, rc):
         if rc:
@@ -215,6 +238,39 @@ class Engine:
 
     def sync(self, q, qb, qp):
         self._check(lib().hnumo_sync(self.h, *self._state_ptrs(q, qb, qp)))
+
+    # ---- run diagnostics on the device state (hnumo_diag_geometry / hnumo_diagnostics)
+    def diag_geometry(self, coord, wjac_df=None):
+        """The grid data of diagnostics(): coord(2 or 3, npoin) = mod_grid coord and, optionally,
+        wjac_df(npoin) (default: the nodal jac of the case).  Engine() calls it when the case
+        carries `coord`."""
+        npoin = self.dims["npoin"]
+        coord = np.asfortranarray(coord, dtype=np.float64)
+        if coord.ndim != 2 or coord.shape[1] != npoin:
+            raise ValueError(f"coord: shape {coord.shape}, expected (2 or 3, {npoin})")
+        cp = coord.ctypes.data_as(C.POINTER(C.c_double))
+        wp = None
+        if wjac_df is not None:
+            w = np.ascontiguousarray(np.asarray(wjac_df, dtype=np.float64).reshape(-1, order="F"))
+            if w.size != npoin:
+                raise ValueError(f"wjac_df: {w.size} elements, expected {npoin}")
+            wp = w.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(lib().hnumo_diag_geometry(self.h, cp, coord.shape[0], wp))
+
+    def diagnostics(self, mass: bool = True) -> dict:
+        """The reference's run diagnostics (print_diagnostics.F90) of the state on the device,
+        computed there: no sync.  Keys cfl_b, cfl, min_dx, min_dy, qbmax, qbmin (4), mass (L; zeros
+        with mass=False, which skips the one sequential sum), qmax, qmin (5, L)."""
+        L = self.dims["nlayers"]
+        out = np.zeros(12 + 11 * L)
+        self._check(lib().hnumo_diagnostics(self.h, DIAG_MASS if mass else 0, _dp(out), out.size))
+        return unpack_diagnostics(out, L)
+
+    def layer_fields(self):
+        """q(5,npoin,nlayers) of diagnostics.F90:24-45 for the state on the device."""
+        out = np.zeros((5, self.dims["npoin"], self.dims["nlayers"]), order="F")
+        self._check(lib().hnumo_layer_fields(self.h, _dp(out), out.size))
+        return out
 
     def bench_steps(self, nsteps: int):
         t = C.c_double()

@@ -83,7 +83,9 @@ module hnumo_engine_c
         hnumo_ti_barotropic_ssprk, hnumo_btp_bcl_coeffs, hnumo_create_rhs_btp, hnumo_get_field_c, &
         hnumo_set_resident, hnumo_sync, hnumo_last_error_c, hnumo_last_error, hnumo_get_field, &
         hnumo_set_summation, hnumo_get_summation, hnumo_stage_path, hnumo_persistent_info, hnumo_predict, &
-        hnumo_rccl_unique_id, hnumo_persistent_stats
+        hnumo_rccl_unique_id, hnumo_persistent_stats, hnumo_diag_geometry, hnumo_diagnostics, &
+        hnumo_layer_fields
+    integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
 
     interface
         integer(c_int) function hnumo_engine_create(mesh, statics, params, halo, device, eng) &
@@ -207,6 +209,36 @@ module hnumo_engine_c
             type(c_ptr), value :: eng
             real(c_double), intent(out) :: q_df(*), qb_df(*), qprime_df(*)
         end function hnumo_sync
+
+        ! Run diagnostics on the device state (see include/hnumo_engine.h).  Once per engine:
+        ! coord(ldc,npoin) = mod_grid coord (ldc = size(coord,1), 2 or 3), wjac_df(npoin) =
+        ! c_loc(wjac_df) of mod_initial, or c_null_ptr: the nodal jac of the mesh descriptor
+        integer(c_int) function hnumo_diag_geometry(eng, coord, ldc, wjac_df) bind(C, name='hnumo_diag_geometry')
+            import :: c_int, c_int32_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: coord(*)
+            integer(c_int32_t), value :: ldc
+            type(c_ptr), value :: wjac_df
+        end function hnumo_diag_geometry
+
+        ! = the numbers of print_diagnostics_mlswe (print_diagnostics.F90:14-190) without hnumo_sync:
+        ! out(12 + 11*nlayers) = [cfl_b, cfl, min_dx, min_dy, qbmax(4), qbmin(4)], then per layer
+        ! [mass, qmax(5), qmin(5)]; flags = HNUMO_DIAG_MASS includes the layer masses
+        integer(c_int) function hnumo_diagnostics(eng, flags, out, n) bind(C, name='hnumo_diagnostics')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: flags
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_diagnostics
+
+        ! = q(5,npoin,nlayers) of diagnostics.F90:24-45 from the device state; n = 5*npoin*nlayers
+        integer(c_int) function hnumo_layer_fields(eng, out5, n) bind(C, name='hnumo_layer_fields')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out5(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_layer_fields
     end interface
 
 contains

@@ -218,6 +218,39 @@ int hnumo_get_field(hnumo_engine *eng, const char *name, double *out, int64_t n)
 int hnumo_set_resident(hnumo_engine *eng, int on);
 int hnumo_sync(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime_df);
 
+/* Run diagnostics on the device state (additive in ABI v10): what the reference's time loop
+ * reports every irestart steps (mod_time_loop.F90:219-254, print_diagnostics.F90:14-190), formed
+ * by HIP kernels from q_df and qb_df where they live and returned as a few hundred bytes -- no
+ * hnumo_sync.  Every value has the bits the reference's host routines give on the synced state.
+ *
+ * hnumo_diag_geometry: once per engine (again after the grid moved).  coord(ldc,npoin), ldc = 2
+ *   or 3, is mod_grid coord, rows 1-2 are read; wjac_df(npoin) is mod_initial wjac_df, NULL: the
+ *   nodal jac of the mesh descriptor (the same numbers).  Builds the running minima of the
+ *   sub-cell sizes of courant_cube_mlswe (courant.F90:95-99) -- the reference divides each cell's
+ *   velocity by the minimum over the cells up to that one in its loop order, not by the grid's
+ *   minimum.  Returns 4 on a NULL coord or another ldc.
+ * hnumo_diagnostics: n = 12 + 11*nlayers,
+ *   out = [cfl_b, cfl, min_dx, min_dy, qbmax(1:4), qbmin(1:4)], then per layer
+ *         [mass, qmax(1:5), qmin(1:5)]
+ *   cfl_b, cfl, min_dx, min_dy = courant_cube_mlswe (courant.F90:34-127); qmax/qmin the extrema
+ *   over the nodes of h, u, v, dp and the interface elevation (diagnostics.F90:24-45), qbmax/qbmin
+ *   those of qb_df (print_diagnostics.F90:60-86); mass = compute_conserved (compute_conserved.F90:
+ *   29-41), summed in node order as there.  flags bit 0: include the layer masses (one sequential
+ *   chain per layer; clear: the mass slots are 0).  Multi-rank engines report their own elements
+ *   (the owned ones of a ghost-layer partition), as each rank of the reference does before its
+ *   mpi_reduce; the host combines ranks.  Works on the state on the device: between the steps of
+ *   a resident engine, or after the last call of a non-resident one; ordered after the step in
+ *   flight on the engine's stream, outside the captured step.  Returns 4 if n is wrong, before
+ *   hnumo_diag_geometry, or before any state was uploaded.  Non-finite states are out of contract
+ *   (the step returns 2 for them); the sign of an extremum that is exactly zero is unspecified.
+ * hnumo_layer_fields: q(5,npoin,nlayers) of diagnostics.F90:24-45 (h, u, v, dp, interface
+ *   elevation), the input of the reference's snapshot writers (diagnostics.F90:58-92), computed
+ *   on the device; n = 5*npoin*nlayers.                                                      */
+#define HNUMO_DIAG_MASS 1
+int hnumo_diag_geometry(hnumo_engine *eng, const double *coord, int32_t ldc, const double *wjac_df);
+int hnumo_diagnostics(hnumo_engine *eng, int32_t flags, double *out, int64_t n);
+int hnumo_layer_fields(hnumo_engine *eng, double *out5, int64_t n);
+
 /* Summation order of the barotropic stage (no reference counterpart: the reference has
  * one order).  HNUMO_SUM_REFERENCE (the default) evaluates the volume integral and the
  * nodal -> quad interpolation as the reference's dense psih/dpsidx sums in its order:
