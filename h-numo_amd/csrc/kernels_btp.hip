@@ -258,7 +258,8 @@ struct StageCfg {
   // SF variant also uses for the interpolation partials Y [NYV][NGL][NQ] (A2 -> B)
   static constexpr int NQV = (SF || QPM) ? 8 : 7, NYV = 7;
   // (SLIM: no Laplacian / new-state buffers; the face-quad traces of FPRE, A2 -> B, share the W
-  // region with qq and rhs, D -> E)
+  // region with qq and rhs, D -> E.  O_QN: the per-stage kernel's new state; the persistent
+  // sub-cycle updates s_qb in place and knows these words only as the tail of FPRE's traces)
   static constexpr int O_QV = QPM ? al2(O_WN + 8 * NGL) : O_WN + 8 * NGL, O_GR = ev(O_QV + NQV * Q), O_FQ = O_GR + 4 * P, O_FL = O_FQ + 16 * NQ,
                        O_W = O_FL + 8 * NGL, O_QQ = O_W, O_RHS = O_QQ + 4 * P, O_LAP = O_RHS + (LEAN ? 0 : 3 * P),
                        O_QN = O_LAP + ((SLIM || LEAN) ? 0 : 2 * P), O_Y = O_W,
@@ -491,8 +492,10 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   // [3][P], [2][P] (LEAN: in the term buffer that is dead in the last D phase)
   double *s_rhs = C::LEAN ? S + C::O_B + C::TB_LAST : S + C::O_RHS;
   double *s_lap = C::LEAN ? s_rhs + 3 * P : S + C::O_LAP;
-  // [P][4] (SLIM: in place of the input; LEAN: the other term buffer, dead after D)
-  double *s_qn = C::SLIM ? s_qb : (C::LEAN ? S + C::O_B + C::TB_PREV : S + C::O_QN);
+  // [P][4] (SLIM, and every persistent arena: in place of the input; LEAN: the other term buffer,
+  // dead after D)
+  constexpr bool INPL = PERSIST && !C::SLIM && !C::LEAN;  // in place, s_q0 / s_q2 kept by E1
+  double *s_qn = (C::SLIM || INPL) ? s_qb : (C::LEAN ? S + C::O_B + C::TB_PREV : S + C::O_QN);
   // FPRE: [8][4*NQ] face-quad traces, own side | ghost side (A2 -> B; LEAN: in term buffer 0)
   double *s_fi = C::LEAN ? S + C::O_B + C::TB0 : S + C::O_W;
   double *SI = S + C::O_BIN;       // B inputs
@@ -510,7 +513,8 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   }
   STAGE_MARK(0);
   __builtin_amdgcn_s_setprio(PRIO_B);
-  if (PROF && tid == 0) s_prof[22] = 0;
+  // (persistent, later stages: zeroed behind the previous stage's clocks, see the end of the body)
+  if (PROF && tid == 0 && (!PERSIST || first)) s_prof[22] = 0;
   const bool use_q0 = !a.rhs_only && a.a1 != 0.0, use_q2 = !a.rhs_only && a.a3 != 0.0;
   const int qpm = (SF || !m.botfr || !a.qpq) ? 0 : a.qpq_mode;  // see StageArgs::qpq
   if (!DBGX(4096)) {
@@ -549,20 +553,12 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     }
   }
   if constexpr (PERSIST) {
-    // the element's state stays in LDS from stage to stage: the previous stage's result
-    // (s_qn) becomes the input, and the Shu-Osher states qb0 / qb2 are kept copies of it.
-    // Stage 0 reads the sub-cycle input written by the previous launch.
-    if constexpr (C::SLIM) {  // (s_qn is s_qb; qb0 / qb2 are saved below)
-      if (first)
-        for (int t = tid; t < 4 * P; t += BS) s_qb[t] = a.qb_in[(size_t)e * 4 * P + t];
-    } else {
-      for (int t = tid; t < 4 * P; t += BS) {
-        const double x = first ? a.qb_in[(size_t)e * 4 * P + t] : s_qn[t];
-        s_qb[t] = x;
-        if (a.first_of_step) s_q0[t] = x;
-        if (a.save_q2) s_q2[t] = x;
-      }
-    }
+    // the element's state stays in LDS from stage to stage: E1 writes the new state over the stage
+    // input (s_qn is s_qb) and keeps the Shu-Osher states qb0 / qb2 (SLIM: saved below; otherwise
+    // s_q0 / s_q2, saved by E1's lane of each node before it overwrites the input), so a later stage
+    // has nothing to copy here.  Stage 0 reads the sub-cycle input written by the previous launch.
+    if (first)
+      for (int t = tid; t < 4 * P; t += BS) s_qb[t] = a.qb_in[(size_t)e * 4 * P + t];
   }
   // Register loads for this thread's quad-point task in B (quad point tid), issued before
   // the wait so they overlap the LDS copies and the interpolation: the remaining quad
@@ -593,11 +589,16 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     load_pre();
     __syncthreads();  // the async LDS copies have landed
   } else {
-    // persistent, later stages: the B inputs re-fetched in the previous stage's E1 must have
-    // landed (this wave's copies; the barrier covers the
-    // others').  The register loads go out after the wait, so it does not cover them.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    LDS_BARRIER();
+    // persistent, later stages: nothing to wait for.  The B inputs re-fetched in the previous
+    // stage's E1 landed before its barrier in front of E2 (each wave waited for its own copies
+    // there), the state is in place, and no wave waits for the acknowledgement of the trace
+    // granules it has just stored: they stay in flight behind the interpolation.  (The slim N=7
+    // arena keeps its wait and barrier here, and the full barrier of the stage loop: without them
+    // dg25N7L3 measured 0.5 % slower, EXPERIMENTS.md §1.)
+    if constexpr (C::SLIM) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      LDS_BARRIER();
+    }
     load_pre();
   }
   STAGE_MARK(21);
@@ -1806,9 +1807,21 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
 #pragma unroll
     for (int v = 1; v < 4; v++) {
       double x = 0.0;
-      if (a.a1 != 0.0) x = a.a1 * ((C::SLIM || C::LEAN) ? r_q0[v - 1] : s_q0[p * 4 + v]);
-      x = x + a.a2 * s_qb[p * 4 + v];
-      if (a.a3 != 0.0) x = x + a.a3 * ((C::SLIM || C::LEAN) ? r_q2[v - 1] : s_q2[p * 4 + v]);
+      if constexpr (INPL) {
+        // this lane is the only reader of the node's input after D and overwrites it below; it
+        // keeps the Shu-Osher copies of it first (component 0 of them is never read) and takes a
+        // copy it has just saved from its register
+        const double xb = s_qb[p * 4 + v];
+        if (a.first_of_step) s_q0[p * 4 + v] = xb;
+        if (a.save_q2) s_q2[p * 4 + v] = xb;
+        if (a.a1 != 0.0) x = a.a1 * (a.first_of_step ? xb : s_q0[p * 4 + v]);
+        x = x + a.a2 * xb;
+        if (a.a3 != 0.0) x = x + a.a3 * (a.save_q2 ? xb : s_q2[p * 4 + v]);
+      } else {
+        if (a.a1 != 0.0) x = a.a1 * ((C::SLIM || C::LEAN) ? r_q0[v - 1] : s_q0[p * 4 + v]);
+        x = x + a.a2 * s_qb[p * 4 + v];
+        if (a.a3 != 0.0) x = x + a.a3 * ((C::SLIM || C::LEAN) ? r_q2[v - 1] : s_q2[p * 4 + v]);
+      }
       qn[v] = x + a.dtt * rh[v - 1];
     }
     qn[0] = qn[1] + (C::SLIM ? r_pb : s_ns[NE_PB * P + p]);
@@ -1857,6 +1870,11 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       for (int c = 0; c < 4; c++) s_grad[c * P + p] = g[c];
     }
   }
+  // persistent: each wave's LDS-DMA copies of the re-fetch above have landed before it passes the
+  // barrier, which so also orders them before their readers in the next stage.  Only they are
+  // outstanding here -- the wait comes before this stage's first trace store, and nothing waits for
+  // those.  (Not the slim arena: it waits at the head of the next stage, see there.)
+  if constexpr (PERSIST && !C::SLIM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   LDS_BARRIER();
   STAGE_MARK(4);
 
@@ -1924,6 +1942,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       }
       s_prof[31] = wall_clock64();
       for (int k = 0; k < 32; k++) a.prof[(size_t)e * 32 + k] = s_prof[k];
+      if (PERSIST) s_prof[22] = 0;  // the next stage's longest trace wait (the stage loop's barrier follows)
     }
   }
 }
@@ -2030,7 +2049,14 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
   }
 #pragma unroll 1
   for (int stage = 1; stage < NS; stage++) {
-    __syncthreads();
+    // the one barrier between a stage's last trace store and the next stage's interpolation: an LDS
+    // barrier, not __syncthreads(), whose release fence would wait for the acknowledgement of the
+    // trace granules just stored (write-through, from beyond the L2) that nobody needs -- a consumer
+    // polls the granule's own tag (dg25L3 2.28 -> 2.22 ms per step; EXPERIMENTS.md §1)
+    if constexpr (C::SLIM)
+      __syncthreads();
+    else
+      LDS_BARRIER();
     // opaque per stage: keeps the body's per-thread index math from being hoisted out of the
     // stage loop (it would stay live across every phase)
     int tid_s = tid, e_s = e;
