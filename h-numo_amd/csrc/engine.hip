@@ -23,6 +23,7 @@
 
 #include "../../include/hnumo_engine.h"
 #include "engine_internal.h"
+#include "setup_plan.h"
 #include "kernels_bcl.hip"
 #include "kernels_btp.hip"
 #include "kernels_lapq.hip"
@@ -133,9 +134,7 @@ struct hnumo_engine {
   // the listed faces and unpack the neighbour's into side 2.
   bool face_halo = false;
   int NS = 0;
-  struct FNbr {
-    int rank = -1, off = 0, n = 0;
-  };
+  using FNbr = SetupPlan::FNbr;
   std::vector<FNbr> fnb;
   int *d_sface = nullptr;                    // [NS] local face of each shared slot
   double *bx_sbuf = nullptr, *bx_rbuf = nullptr;  // [NS * per-face message] baroclinic exchanges
@@ -304,8 +303,12 @@ struct Launch {
       hipLaunchKernelGGL((btp_stage_kernel<NGL, NQ, false, NB, ACCF>), dim3(n), dim3(K::BS), 0, st, a);
   }
   static void subcycle(hnumo_engine *e, const StageArgs *stages, int ns) {
-    SubArgs sa{stages, ns, e->epoch, e->sub_done, e->sub_arrive, e->neg_flag, e->dbg_abort_epoch, e->d_eperm};
-    if (e->summation == HNUMO_SUM_REFERENCE)
+    launch_sub(e, e->summation, SubArgs{stages, ns, e->epoch, e->sub_done, e->sub_arrive, e->neg_flag, e->dbg_abort_epoch,
+                                        e->d_eperm});
+  }
+  // the persistent grid in summation mode `sum`: a sub-cycle's stages (subcycle) or none (probe)
+  static void launch_sub(hnumo_engine *e, int sum, const SubArgs &sa) {
+    if (sum == HNUMO_SUM_REFERENCE)
       hipLaunchKernelGGL((btp_subcycle_kernel<NGL, NQ, false>), dim3(e->nelem_owned),
                          dim3(StageCfg<NGL, NQ, false>::BS), e->persist_pad, e->stream, sa);
     else
@@ -336,13 +339,7 @@ struct Launch {
   }
   // the trial launch: the persistent grid with no stages, i.e. the residency rendezvous alone
   static void probe(hnumo_engine *e, int sum) {
-    SubArgs sa{e->d_stages[0], 0, e->epoch, e->sub_done, e->sub_arrive, e->neg_flag, nullptr, e->d_eperm};
-    if (sum == HNUMO_SUM_REFERENCE)
-      hipLaunchKernelGGL((btp_subcycle_kernel<NGL, NQ, false>), dim3(e->nelem_owned),
-                         dim3(StageCfg<NGL, NQ, false>::BS), e->persist_pad, e->stream, sa);
-    else
-      hipLaunchKernelGGL((btp_subcycle_kernel<NGL, NQ, true>), dim3(e->nelem_owned), dim3(StageCfg<NGL, NQ, true>::BS),
-                         e->persist_pad, e->stream, sa);
+    launch_sub(e, sum, SubArgs{e->d_stages[0], 0, e->epoch, e->sub_done, e->sub_arrive, e->neg_flag, nullptr, e->d_eperm});
   }
   // face traces of elements [e0, e0+n) into their neighbours' slots
   static void grad_trace(hnumo_engine *e, const double *qb, double *gt, int e0, int n, TraceGranule *gtr = nullptr) {
@@ -464,8 +461,6 @@ struct Launch {
     case 8: Launch<8, 15>::CALL; break;                                         \
     default: break;                                                             \
   }
-
-static bool supported_ngl(int ngl) { return ngl == 3 || ngl == 4 || ngl == 5 || ngl == 6 || ngl == 8; }
 
 // ------------------------------------------------------------------ step pieces
 __global__ void copy_kernel(double *dst, const double *src, size_t n) {
@@ -1021,15 +1016,305 @@ static void launch_step(hnumo_engine *e) {
     hipLaunchKernelGGL(finite_check_kernel, dim3(256), dim3(256), 0, e->stream, e->q, n3, e->neg_flag);
 }
 
-// ------------------------------------------------------------------ C ABI
-extern "C" {
-
-int hnumo_abi_version(void) { return HNUMO_ABI_VERSION; }
-
 static int fail(hnumo_engine *eng, int code, const std::string &msg) {
   eng->err = msg;
   return code;
 }
+
+// ------------------------------------------------------------------ engine creation
+// The steps of hnumo_engine_create, in its order.  What depends on the descriptors alone -- their
+// validation, the connectivity tables, the repacked statics -- is build_setup_plan's
+// (setup_plan.h, host only); the steps here give the plan a device.
+
+// dalloc and a synchronous copy of a host table into it.  A failed allocation is left to the
+// caller's alloc_failed check, as with dalloc.
+template <typename T>
+static hipError_t dupload(hnumo_engine *eng, const std::vector<T> &v, T *&dst) {
+  dst = dalloc<T>(eng, v.size());
+  if (!dst || v.empty()) return hipSuccess;
+  return hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// sizes, parameters and the halo summary of the plan
+static void adopt_plan(hnumo_engine *eng, const hnumo_mesh_desc *mesh, const hnumo_static_desc *st,
+                       const hnumo_params *par, const hnumo_halo_desc *halo, const SetupPlan &pl) {
+  eng->p = *par;
+  const int E = mesh->nelem, ngl = mesh->ngl, nq = mesh->nq, F = mesh->nface, L = mesh->nlayers;
+  const int P = ngl * ngl, Q = nq * nq;
+  eng->nelem = E; eng->npoin = E * P; eng->npq = E * Q; eng->nface = F; eng->ngl = ngl; eng->nq = nq;
+  eng->L = L; eng->P = P; eng->Q = Q; eng->K = par->kstages;
+  eng->nelem_owned = pl.nelem_owned;
+  eng->FQ = (size_t)F * nq; eng->FN = (size_t)F * ngl;
+  eng->face_halo = pl.face_halo;
+  eng->NS = pl.NS;
+  eng->fnb = pl.fnb;
+  eng->fslotA = pl.fslotA;
+  eng->lapq_on = par->method_visc == 1;
+  if (pl.face_halo || (halo && halo->nranks > 1)) {
+    eng->rank = halo->rank;
+    eng->nranks = halo->nranks;
+  }
+  eng->ssprk_a.assign(st->ssprk_a, st->ssprk_a + 3 * par->kstages);
+  eng->ssprk_beta.assign(st->ssprk_beta, st->ssprk_beta + par->kstages);
+}
+
+static int open_device(hnumo_engine *eng, int *ncu) {
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamCreateWithFlags(&eng->stream, hipStreamNonBlocking));
+  HIPCHK(hipEventCreate(&eng->ev0));
+  HIPCHK(hipEventCreate(&eng->ev1));
+  HIPCHK(hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, eng->device));
+  return 0;
+}
+
+// what the environment asks for beyond the engine's own fields
+struct Knobs {
+  bool qpq = false, stage_prof = false;  // buffers to allocate
+  bool persist_on = true, place = false, glue_perm = false;
+};
+
+// every environment setting of create, read here and in this order (hnumo_overrides lists them in it)
+static int read_knobs(hnumo_engine *eng, int ncu, Knobs &k) {
+  if (const char *ge = env_knob(eng, "HNUMO_GRAPH", false)) eng->graph_env = ge[0] == '0' ? 0 : ge[0] == '1' ? 1 : -1;
+  if (const char *sm = env_knob(eng, "HNUMO_SUMMATION", false)) {
+    if (!strcmp(sm, "reference"))
+      eng->summation = HNUMO_SUM_REFERENCE;
+    else if (!strcmp(sm, "factored"))
+      eng->summation = HNUMO_SUM_FACTORED;
+    else
+      return fail(eng, HNUMO_ERR_INVALID, std::string("HNUMO_SUMMATION=") + sm + ": only 'reference' or 'factored'");
+  }
+  if (HNUMO_DIAG)  // (diagnostics builds only; see engine_internal.h)
+    if (const char *sd = env_knob(eng, "HNUMO_STAGE_DBG")) eng->stage_dbg = atoi(sd);
+  if (const char *fz = env_knob(eng, "HNUMO_FUSE")) eng->no_fuse = fz[0] == '0';
+  // (bit 1 drops a required stream dependency -- wrong results, timing only: diagnostics builds)
+  if (HNUMO_DIAG)
+    if (const char *sd = env_knob(eng, "HNUMO_SCHED_DBG")) eng->sched_dbg = atoi(sd);
+  // per-stage kernel arena: on meshes that take several residency rounds per stage, the arena
+  // sized for 4 workgroups per CU (1-row term chunks) -- 1.566 -> 1.517 ms per stage at C4
+  // (tools/ab_env.py, round 2); small meshes keep the 3-per-CU arena
+  // large meshes: the LEAN 5-per-CU arena (C4: 1.331 ms per stage against 1.409 for the 4-per-CU
+  // one with 2-row term chunks and 1.501 for round 2's, profiles/r03f)
+  eng->stage_nb = eng->nelem_owned >= 2048 ? 5 : 0;
+  if (const char *sn = env_knob(eng, "HNUMO_STAGE_NB")) eng->stage_nb = atoi(sn);
+  eng->bcl_big = eng->nelem_owned >= 2048;
+  if (const char *bb = env_knob(eng, "HNUMO_BCL_BIG")) eng->bcl_big = bb[0] == '1';
+  if (const char *az = env_knob(eng, "HNUMO_ACC_ZERO")) eng->acc_zero = az[0] == '1';
+  {
+    const char *qv = env_knob(eng, "HNUMO_QPQ");
+    k.qpq = eng->p.botfr && !(qv && atoi(qv) == 0);
+  }
+  if (const char *sp = HNUMO_DIAG ? env_knob(eng, "HNUMO_STAGE_PROF") : nullptr) k.stage_prof = sp[0] == '1';
+  const char *pe = env_knob(eng, "HNUMO_PERSISTENT", false);
+  k.persist_on = !(pe && pe[0] == '0');
+  if (k.persist_on) {
+    if (const char *pp = env_knob(eng, "HNUMO_PERSIST_LDS_PAD")) eng->persist_pad = std::max(0, atoi(pp));
+    // HNUMO_PERSIST_GUARD: 0 none (the in-launch rendezvous alone), 'estimate', 'trial', 1 both
+    if (const char *pg = env_knob(eng, "HNUMO_PERSIST_GUARD"))
+      eng->persist_guard = pg[0] == '0' ? 0 : pg[0] == 'e' ? 1 : pg[0] == 't' ? 2 : 3;
+    // the persistent sub-cycle's placement (placement_perm; HNUMO_PERSIST_PERM=0: the identity), on
+    // single-rank engines whose elements do not divide evenly among the CUs
+    const char *pm = env_knob(eng, "HNUMO_PERSIST_PERM");
+    const int E = eng->nelem;
+    k.place = !(pm && pm[0] == '0') && ncu > 0 && E % ncu && eng->nranks == 1 && !eng->face_halo && eng->comm_mode == 0 &&
+              eng->nelem_owned == E;
+    if (k.place) {
+      // the element kernels of the step (625 blocks at dg25 too: the same CUs hold one block more)
+      const char *pg = env_knob(eng, "HNUMO_GLUE_PERM");
+      k.glue_perm = !(pg && pg[0] == '0');
+    }
+  }
+  return 0;
+}
+
+// every device buffer that does not belong to the halo or the persistent sub-cycle; the plan's
+// tables are uploaded as they are allocated
+static int create_buffers(hnumo_engine *eng, const SetupPlan &pl, const hnumo_static_desc *st, const Knobs &k) {
+  const int E = eng->nelem, ngl = eng->ngl, nq = eng->nq, L = eng->L, P = eng->P, Qe = eng->Q;
+  const size_t npoin = eng->npoin, npq = eng->npq, FQ = eng->FQ, FN = eng->FN;
+  HIPCHK(dupload(eng, pl.conn, eng->iconn));
+  HIPCHK(dupload(eng, pl.hb, eng->basis));
+  HIPCHK(dupload(eng, pl.qs, eng->qstat));
+  HIPCHK(dupload(eng, pl.ns, eng->nstat));
+  HIPCHK(dupload(eng, pl.fs, eng->fstat));
+  HIPCHK(dupload(eng, pl.fns, eng->fnstat));
+  HIPCHK(dupload(eng, pl.qsE, eng->qstatE));
+  HIPCHK(dupload(eng, pl.nsE, eng->nstatE));
+  HIPCHK(dupload(eng, pl.efs, eng->efstat));
+  eng->ecoef = dalloc<double>(eng, (size_t)E * eco_stride(Qe, P));
+  eng->efcoef = dalloc<double>(eng, (size_t)E * 4 * (4 * nq + 10 * ngl));
+  HIPCHK(dupload(eng, std::vector<double>(st->alpha, st->alpha + L), eng->alpha));
+  HIPCHK(dupload(eng, std::vector<double>(st->tau_wind, st->tau_wind + 2 * npq), eng->tau_wind));
+  const size_t n3 = 3 * npoin * L;
+  eng->q = dalloc<double>(eng, n3); eng->qp = dalloc<double>(eng, n3); eng->qb = dalloc<double>(eng, 4 * npoin);
+  eng->q2 = dalloc<double>(eng, n3); eng->qp2 = dalloc<double>(eng, n3); eng->qbp = dalloc<double>(eng, 4 * npoin);
+  eng->qf = dalloc<double>(eng, 6 * FN * L); eng->qf2 = dalloc<double>(eng, 6 * FN * L);
+  eng->qfa = dalloc<double>(eng, 6 * FN * L);
+  eng->dpp2 = dalloc<double>(eng, npoin * L);
+  for (int i = 0; i < 4; i++) eng->qbuf[i] = dalloc<double>(eng, 4 * npoin);
+  // trace buffers: element slots [4E], then (processor-face halo) NS send + NS receive slots
+  for (int i = 0; i < 2; i++) eng->gtrace[i] = dalloc<double>(eng, (4 * (size_t)E + 2 * (size_t)eng->NS) * 8 * ngl);
+  eng->qcoef = dalloc<double>(eng, QC_N * npq); eng->ncoef = dalloc<double>(eng, NC_N * npoin);
+  eng->fcoef = dalloc<double>(eng, FC_N * FQ); eng->fncoef = dalloc<double>(eng, 10 * FN);
+  eng->dpp_graduv = dalloc<double>(eng, 4 * npoin * L); eng->dpprime_visc = dalloc<double>(eng, npoin * L);
+  eng->gdpp_face = dalloc<double>(eng, 10 * FN * L);
+  eng->qacc = dalloc<double>(eng, QA_N * npq); eng->facc = dalloc<double>(eng, FA_N * 4 * (size_t)E * nq);
+  eng->nacc = dalloc<double>(eng, NA_N * npoin); eng->gfacc = dalloc<double>(eng, 8 * 4 * (size_t)E * ngl);
+  eng->tau_wind_ave = dalloc<double>(eng, 2 * npq);
+  eng->slmf = dalloc<double>(eng, 2 * npq); eng->slmf_face = dalloc<double>(eng, 2 * FQ);
+  eng->dpp = dalloc<double>(eng, npoin * L);
+  eng->fmass = dalloc<double>(eng, FQ * L); eng->fcons = dalloc<double>(eng, FQ * L);
+  eng->momL = dalloc<double>(eng, 4 * (size_t)E * 2 * nq * L);  // [slot][L][2][NQ] (MSLOT)
+  eng->momR = nullptr;
+  eng->lapf = dalloc<double>(eng, 4 * (size_t)E * 2 * ngl * L);  // [slot][L][2][NGL]
+  if (eng->lapq_on) {  // quad-point LDG (kernels_lapq.hip)
+    eng->dpq = dalloc<double>(eng, npq * L);
+    eng->lq_flux = dalloc<double>(eng, 4 * npq * L);
+    eng->lapq = dalloc<double>(eng, 2 * npoin * L);
+    HIPCHK(dupload(eng, pl.fq, eng->fqLR));
+  }
+  eng->rhs = dalloc<double>(eng, 3 * npoin);
+  eng->neg_flag = dalloc<int>(eng, 1);
+  if (k.qpq) eng->qpq = dalloc<double>(eng, (size_t)E * 3 * nq * nq);
+  if (k.stage_prof) eng->stage_prof = dalloc<unsigned long long>(eng, (size_t)E * 32);
+  eng->steps_done = dalloc<unsigned>(eng, 1);
+  if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (out of device memory?)");
+  HIPCHK(hipHostMalloc((void **)&eng->h_neg, sizeof(int)));
+  HIPCHK(hipHostMalloc((void **)&eng->h_steps, sizeof(unsigned)));
+  return 0;
+}
+
+// RCCL point-to-point over xGMI, for either halo kind
+static int init_rccl(hnumo_engine *eng, const hnumo_halo_desc *halo) {
+  if (!halo->comm_id) return 0;
+  ncclUniqueId id;
+  static_assert(sizeof(ncclUniqueId) == 128, "RCCL unique id size");
+  std::memcpy(&id, halo->comm_id, sizeof(id));
+  ncclResult_t nr = ncclCommInitRank(&eng->comm, halo->nranks, id, halo->rank);
+  if (nr != ncclSuccess) return fail(eng, HNUMO_ERR_DEVICE, std::string("ncclCommInitRank: ") + ncclGetErrorString(nr));
+  eng->comm_mode = 2;
+  return 0;
+}
+
+// the halo's lists and message buffers, the second stream of the processor-face schedule, the communicator
+static int create_halo(hnumo_engine *eng, const SetupPlan &pl, const hnumo_halo_desc *halo) {
+  const int ngl = eng->ngl, nq = eng->nq, L = eng->L, NS = eng->NS;
+  if (eng->face_halo) {
+    eng->nB = (int)pl.elB.size();
+    eng->nI = (int)pl.elI.size();
+    int *d_tsrc = nullptr;
+    HIPCHK(dupload(eng, pl.tsrc, d_tsrc));
+    HIPCHK(dupload(eng, pl.sface, eng->d_sface));
+    HIPCHK(dupload(eng, pl.elB, eng->d_elB));
+    HIPCHK(dupload(eng, pl.elI, eng->d_elI));
+    eng->cdef = dalloc<double>(eng, 4 * eng->FQ * L);
+    eng->bx_per_max = (size_t)L * std::max({5 * ngl, 2 * nq, eng->lapq_on ? 4 * nq : 0});
+    eng->bx_sbuf = dalloc<double>(eng, eng->bx_per_max * NS);
+    eng->bx_rbuf = dalloc<double>(eng, eng->bx_per_max * NS);
+    if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (halo buffers)");
+    eng->m.etsrc = d_tsrc;
+    // the boundary elements and their transport are the critical path of the stage chain:
+    // their stream gets the highest priority, so their workgroups dispatch ahead of the
+    // interior launch's
+    int prio_lo = 0, prio_hi = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    HIPCHK(hipStreamCreateWithPriority(&eng->stream2, hipStreamNonBlocking, prio_hi));
+    for (hipEvent_t *ev : {&eng->ev_fork, &eng->ev_join, &eng->ev_I, &eng->ev_B[0], &eng->ev_B[1], &eng->ev_tsent,
+                           &eng->ev_bpacked, &eng->ev_bdone})
+      HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    for (hipEvent_t *ev : {&eng->ev_Is, &eng->ev_Bs[0], &eng->ev_Bs[1]}) HIPCHK(hipEventCreate(ev));
+    return init_rccl(eng, halo);
+  }
+  if (halo && halo->nranks > 1) {
+    const size_t per_max = (size_t)eng->P * std::max(4, 3 * L);
+    for (const auto &g : pl.gnb) {
+      Neighbour nb;
+      nb.rank = g.rank;
+      nb.nsend = (int)g.send.size();
+      nb.nrecv = (int)g.recv.size();
+      HIPCHK(dupload(eng, g.send, nb.d_send));
+      HIPCHK(dupload(eng, g.recv, nb.d_recv));
+      nb.sbuf = dalloc<double>(eng, nb.nsend * per_max);
+      nb.rbuf = dalloc<double>(eng, nb.nrecv * per_max);
+      if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (halo buffers)");
+      eng->nbh.push_back(nb);
+    }
+    return init_rccl(eng, halo);
+  }
+  return 0;
+}
+
+static void fill_devmesh(hnumo_engine *eng, const SetupPlan &pl) {
+  DevMesh &m = eng->m;
+  const hnumo_params &par = eng->p;
+  const SetupPlan::ConnOff &o = pl.off;
+  m.nelem = eng->nelem; m.npoin = eng->npoin; m.npoin_q = eng->npq; m.nface = eng->nface; m.ngl = eng->ngl;
+  m.nq = eng->nq; m.L = eng->L;
+  m.efaces = eng->iconn + o.efaces; m.eside = eng->iconn + o.eside; m.ebc = eng->iconn + o.ebc; m.efmap = eng->iconn + o.efmap;
+  m.enbr_node = eng->iconn + o.enbr_node; m.enbr_e = eng->iconn + o.enbr_e; m.enbr_lf = eng->iconn + o.enbr_lf;
+  m.fnodeL = eng->iconn + o.fnodeL; m.fnodeR = eng->iconn + o.fnodeR; m.fel = eng->iconn + o.fel; m.fer = eng->iconn + o.fer;
+  m.fslotL = eng->iconn + o.fslotL; m.fslotR = eng->iconn + o.fslotR; m.fslotA = eng->iconn + o.fslotA;
+  m.erec = eng->iconn + o.erec;
+  m.qstatE = eng->qstatE; m.nstatE = eng->nstatE; m.efstat = eng->efstat;
+  m.basis = eng->basis; m.basis_pd = eng->basis + pl.nb0; m.qstat = eng->qstat; m.nstat = eng->nstat; m.fstat = eng->fstat; m.fnstat = eng->fnstat;
+  m.alpha = eng->alpha;
+  m.gravity = par.gravity; m.cd = par.cd_mlswe; m.visc = par.visc_mlswe; m.dt = par.dt; m.dt_btp = par.dt_btp;
+  m.botfr = par.botfr;
+  m.ad = par.ad_mlswe; m.max_shear_dz = par.max_shear_dz; m.shear_corr = par.shear_corrector;
+  m.runflag = eng->neg_flag;
+  m.steps_done = eng->steps_done;
+}
+
+// persistent sub-cycle: its buffers, the occupancy estimate, the placement, the stage tables of the
+// two sub-cycles of a step and the residency trial launches
+static int setup_persistent(hnumo_engine *eng, const SetupPlan &pl, const Knobs &k, int ncu) {
+  const int E = eng->nelem, ngl = eng->ngl;
+  eng->epoch = dalloc<unsigned long long>(eng, 1);
+  eng->qsv = dalloc<double>(eng, (size_t)E * 8 * ngl * ngl);
+  eng->sub_done = dalloc<unsigned>(eng, 1);
+  eng->sub_arrive = dalloc<unsigned>(eng, 1);
+  eng->dbg_abort_epoch = dalloc<unsigned long long>(eng, 1);
+  if (eng->dbg_abort_epoch) HIPCHK(hipMemset(eng->dbg_abort_epoch, 0xff, sizeof(unsigned long long)));  // never
+  for (int b = 0; b < 2; b++) eng->gtr[b] = dalloc<TraceGranule>(eng, (size_t)E * 32 * ngl);
+  if (k.persist_on) DISPATCH(eng, occupancy(eng, ncu));
+  if (k.place) {
+    const auto ebc = pl.conn.begin() + pl.off.ebc;
+    HIPCHK(dupload(eng, placement_perm(std::vector<int>(ebc, ebc + 4 * E), E, ncu), eng->d_eperm));
+    if (k.glue_perm) eng->m.eperm = eng->d_eperm;
+  }
+  // the stage tables copy eng->m: built after the placement above, so every DevMesh copy (these,
+  // the per-stage tables of stage_table at run time) carries the same eperm
+  const double *qps[2] = {eng->qp, eng->qp2};
+  for (int v = 0; v < 2; v++) {
+    std::vector<StageArgs> st;
+    (void)stage_table(eng, qps[v], st);
+    st.front().qb_in = eng->qb;                        // the step-start state (launch_subcycle)
+    st.front().self_trace = 1;                         // stage 0 publishes its input traces
+    st.back().qb_out = v == 0 ? eng->qbp : eng->qb;    // predictor / corrector result
+    HIPCHK(dupload(eng, st, eng->d_stages[v]));
+    if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (stage tables)");
+  }
+  if (k.persist_on) {
+    // the trial launches: what the dispatcher does, not what the estimate says, decides
+    for (int sm = 0; sm < 2 && (eng->persist_guard & 2); sm++) {
+      if (!eng->persistent_ok[sm] || eng->comm_mode != 0 || eng->nranks != 1) continue;
+      HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
+      DISPATCH(eng, probe(eng, sm));
+      HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
+      HIPCHK(hipStreamSynchronize(eng->stream));
+      HIPCHK(hipGetLastError());
+      eng->probe_ok[sm] = (*eng->h_neg & RUN_ABORT) ? 0 : 1;
+      if (!eng->probe_ok[sm]) eng->persistent_ok[sm] = false;
+      HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
+    }
+  }
+  return 0;
+}
+
+// ------------------------------------------------------------------ C ABI
+extern "C" {
+
+int hnumo_abi_version(void) { return HNUMO_ABI_VERSION; }
 
 int hnumo_overrides(const hnumo_engine *eng, char *out, int64_t len) {
   if (!eng) return HNUMO_ERR_INVALID;
@@ -1089,610 +1374,22 @@ int hnumo_engine_create(const hnumo_mesh_desc *mesh, const hnumo_static_desc *st
   hnumo_engine *eng = new hnumo_engine();
   *out = eng;
   eng->device = device;
-  if (!mesh || !st || !par) return fail(eng, HNUMO_ERR_INVALID, "null descriptor");
-  // multi-rank: the reference's processor-face lists (num_send_recv / nbh_send_recv), or the
-  // ghost-element lists (num_ghost_send / num_ghost_recv) -- one of the two
-  std::vector<int> sface;                 // processor-face halo: shared slot -> local face
-  std::vector<int> face_slot(mesh->nface > 0 ? mesh->nface : 0, -1);
-  // (nranks == 1 with processor-face lists: the self-neighbour test contract -- every listed face
-  // is shared with this rank itself, so each receives its own side 1 as side 2 over the same
-  // transport code as a real neighbour's; tests/test_rccl_self_gpu.py)
-  if (halo && (halo->nranks > 1 || halo->num_nbh > 0)) {
-    if (halo->rank < 0 || halo->rank >= halo->nranks) return fail(eng, HNUMO_ERR_INVALID, "bad rank");
-    bool any_face = false, any_ghost = false;
-    for (int k = 0; k < halo->num_nbh; k++) {
-      if (halo->num_send_recv && halo->num_send_recv[k] > 0) any_face = true;
-      if ((halo->num_ghost_send && halo->num_ghost_send[k] > 0) || (halo->num_ghost_recv && halo->num_ghost_recv[k] > 0))
-        any_ghost = true;
-    }
-    if (any_face && any_ghost)
-      return fail(eng, HNUMO_ERR_INVALID, "give either processor-face lists or ghost-element lists, not both");
-    if (any_face) {
-      eng->face_halo = true;
-      if (halo->nelem_owned != 0 && halo->nelem_owned != mesh->nelem)
-        return fail(eng, HNUMO_ERR_INVALID, "processor-face halo: every local element is owned (nelem_owned = nelem)");
-      if (!halo->nbh_proc || !halo->num_send_recv || !halo->nbh_send_recv)
-        return fail(eng, HNUMO_ERR_INVALID, "processor-face halo needs nbh_proc, num_send_recv, nbh_send_recv");
-      size_t o = 0;
-      for (int k = 0; k < halo->num_nbh; k++) {
-        hnumo_engine::FNbr nb;
-        nb.rank = halo->nbh_proc[k] - 1;  // mod_parallel nbh_proc is 1-based (p4est.c:1357)
-        nb.off = (int)sface.size();
-        nb.n = halo->num_send_recv[k];
-        if (nb.rank < 0 || nb.rank >= halo->nranks || (nb.rank == halo->rank && halo->nranks > 1))
-          return fail(eng, HNUMO_ERR_INVALID, "nbh_proc: bad neighbour rank (1-based ranks expected)");
-        // mod_parallel lists each neighbour process once (p4est.c:1343-1360); the transports pair a
-        // rank's message with the peer's one entry for it.  The one exception is the self-neighbour
-        // contract (nranks == 1): a W-rank partition's rank emulated on one GPU may keep its real
-        // per-neighbour lists, every one addressed to itself -- one ncclSend/ncclRecv pair per list
-        // inside the group (RCCL matches same-peer operations in issue order), each list's message
-        // at its own offset and size, as on the W-GPU run
-        if (halo->nranks > 1)
-          for (const auto &pn : eng->fnb)
-            if (pn.rank == nb.rank) return fail(eng, HNUMO_ERR_INVALID, "nbh_proc: a neighbour rank is listed twice");
-        if (nb.n < 0) return fail(eng, HNUMO_ERR_INVALID, "num_send_recv < 0");
-        for (int i = 0; i < nb.n; i++) {
-          const int f = halo->nbh_send_recv[o + i] - 1;
-          if (f < 0 || f >= mesh->nface) return fail(eng, HNUMO_ERR_INVALID, "nbh_send_recv: face id out of range");
-          if (mesh->face[8 * f + 7] != 0)
-            return fail(eng, HNUMO_ERR_INVALID, "nbh_send_recv lists a face whose face(8) is not 0 (not a processor face)");
-          if (face_slot[f] >= 0)
-            return fail(eng, HNUMO_ERR_INVALID,
-                        "a processor face is listed twice (non-conforming multiplicity > 1 is not supported)");
-          face_slot[f] = (int)sface.size();
-          sface.push_back(f);
-        }
-        o += nb.n;
-        eng->fnb.push_back(nb);
-      }
-      eng->NS = (int)sface.size();
-    } else {
-      if (halo->nranks < 2) return fail(eng, HNUMO_ERR_INVALID, "ghost-element lists need nranks > 1");
-      if (halo->nelem_owned < 1 || halo->nelem_owned > mesh->nelem)
-        return fail(eng, HNUMO_ERR_INVALID, "nelem_owned must be in 1..nelem (owned elements first)");
-    }
-  }
-  if (par->method_visc == 1) {
-    if (!mesh->imapl_q || !mesh->imapr_q) return fail(eng, HNUMO_ERR_INVALID, "method_visc==1 needs imapl_q/imapr_q");
-    if (halo && halo->nranks > 1 && !eng->face_halo)
-      return fail(eng, HNUMO_ERR_INVALID,
-                  "method_visc==1 (quad-point LDG) runs on one rank or on the processor-face halo, not on ghost elements");
-  }
-  if (par->shear_corrector != HNUMO_SHEAR_CORRECTOR_REFERENCE && par->shear_corrector != HNUMO_SHEAR_CORRECTOR_PREDICTED)
-    return fail(eng, HNUMO_ERR_INVALID, "shear_corrector must be HNUMO_SHEAR_CORRECTOR_REFERENCE or _PREDICTED");
-  if (mesh->nlayers < 1 || mesh->nlayers > MAXL)
-    return fail(eng, HNUMO_ERR_INVALID, "nlayers must be 1..3 (qp(k) quirk, mod_create_rhs_mlswe.F90:382)");
-  if (!supported_ngl(mesh->ngl) || mesh->nq != 2 * mesh->ngl - 1)
-    return fail(eng, HNUMO_ERR_INVALID, "unsupported polynomial order (N in {2,3,4,5,7}, nq=2N+1)");
-  if (par->kstages < 1 || par->kstages > 5 || par->N_btp < 1) return fail(eng, HNUMO_ERR_INVALID, "bad kstages/N_btp");
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipStreamCreateWithFlags(&eng->stream, hipStreamNonBlocking));
-  HIPCHK(hipEventCreate(&eng->ev0));
-  HIPCHK(hipEventCreate(&eng->ev1));
-  eng->p = *par;
-  const int E = mesh->nelem, ngl = mesh->ngl, nq = mesh->nq, F = mesh->nface, L = mesh->nlayers;
-  const int P = ngl * ngl, Q = nq * nq;
-  if (mesh->npoin != E * P || mesh->npoin_q != E * Q) return fail(eng, HNUMO_ERR_INVALID, "npoin/npoin_q mismatch");
-  eng->nelem = E; eng->npoin = E * P; eng->npq = E * Q; eng->nface = F; eng->ngl = ngl; eng->nq = nq;
-  eng->L = L; eng->P = P; eng->Q = Q; eng->K = par->kstages;
-  eng->nelem_owned = (halo && halo->nranks > 1 && !eng->face_halo) ? halo->nelem_owned : E;
-  const int EO = eng->nelem_owned;
-  eng->FQ = (size_t)F * nq; eng->FN = (size_t)F * ngl;
-  const size_t npoin = eng->npoin, npq = eng->npq, FQ = eng->FQ, FN = eng->FN;
-
-  // ---- element -> face connectivity from the reference face arrays
-  std::vector<std::vector<std::pair<int, int>>> ef(E);
-  for (int f = 0; f < F; f++) {
-    int el = mesh->face[8 * f + 6] - 1, er = mesh->face[8 * f + 7];
-    if (el < 0 || el >= E) return fail(eng, HNUMO_ERR_INVALID, "face(7) out of range");
-    ef[el].push_back({f, 0});
-    if (er > 0) {
-      if (er > E) return fail(eng, HNUMO_ERR_INVALID, "face(8) out of range");
-      ef[er - 1].push_back({f, 1});
-    } else if (er == 0 && face_slot[f] < 0) {
-      return fail(eng, HNUMO_ERR_INVALID,
-                  "face(8) = 0 (processor face) but the face is not in the halo's nbh_send_recv lists");
-    }
-  }
-  auto lnode = [&](const int32_t *imap, int f, int n) {
-    int i = imap[3 * (n + ngl * f)] - 1, j = imap[3 * (n + ngl * f) + 1] - 1;
-    return j * ngl + i;
-  };
-  std::vector<int> efaces(4 * E), eside(4 * E), ebc(4 * E), efmap(4 * E * ngl), enbr_node(4 * E * ngl, -1);
-  std::vector<int> enbr_e(4 * E, -1), enbr_lf(4 * E, -1), fnodeL(FN), fnodeR(FN, -1), fel(F), fer(F);
-  for (int e = 0; e < E; e++) {
-    if (ef[e].size() != 4) return fail(eng, HNUMO_ERR_INVALID, "every element needs exactly 4 faces");
-    std::sort(ef[e].begin(), ef[e].end());
-  }
-  for (int e = 0; e < E; e++)
-    for (int lf = 0; lf < 4; lf++) {
-      int f = ef[e][lf].first, s = ef[e][lf].second;
-      int el = mesh->face[8 * f + 6] - 1, er = mesh->face[8 * f + 7];
-      efaces[4 * e + lf] = f;
-      eside[4 * e + lf] = s;
-      ebc[4 * e + lf] = er;
-      for (int n = 0; n < ngl; n++) efmap[(4 * e + lf) * ngl + n] = lnode(s == 0 ? mesh->imapl : mesh->imapr, f, n);
-      if (er > 0) {
-        int nb = s == 0 ? er - 1 : el;
-        enbr_e[4 * e + lf] = nb;
-        for (int k = 0; k < 4; k++)
-          if (ef[nb][k].first == f) enbr_lf[4 * e + lf] = k;
-        for (int n = 0; n < ngl; n++)
-          enbr_node[(4 * e + lf) * ngl + n] = nb * P + lnode(s == 0 ? mesh->imapr : mesh->imapl, f, n);
-      } else if (er == 0) {
-        // processor face: the stage writes this face's traces into send slot 4E + s of the
-        // trace buffer, i.e. "element" E + s/4, local face s%4
-        const int sl = face_slot[f];
-        enbr_e[4 * e + lf] = E + sl / 4;
-        enbr_lf[4 * e + lf] = sl % 4;
-      }
-    }
-  for (int f = 0; f < F; f++) {
-    int el = mesh->face[8 * f + 6] - 1, er = mesh->face[8 * f + 7];
-    fel[f] = el;
-    fer[f] = er;
-    for (int n = 0; n < ngl; n++) {
-      fnodeL[(size_t)f * ngl + n] = el * P + lnode(mesh->imapl, f, n);
-      if (er > 0) fnodeR[(size_t)f * ngl + n] = (er - 1) * P + lnode(mesh->imapr, f, n);
-    }
-  }
-  // face -> element-side slots; per-element int records for the stage kernel
-  std::vector<int> fslotL(F, -1), fslotR(F, -1), fslotA(F, -1);
-  for (int e = 0; e < E; e++)
-    for (int lf = 0; lf < 4; lf++) (eside[4 * e + lf] == 0 ? fslotL : fslotR)[efaces[4 * e + lf]] = 4 * e + lf;
-  // face averages are kept by the left element, or by the right one when the left is a ghost
-  for (int f = 0; f < F; f++) {
-    const int el = fel[f], er = fer[f];
-    fslotA[f] = (el >= EO && er > 0 && er - 1 < EO) ? fslotR[f] : fslotL[f];
-  }
-  const int ERS = EREC_SIZE(ngl);
-  std::vector<int> erec((size_t)E * ERS, -1);
-  for (int e = 0; e < E; e++) {
-    int *r = &erec[(size_t)e * ERS];
-    for (int lf = 0; lf < 4; lf++) {
-      r[EREC_FACE + lf] = efaces[4 * e + lf];
-      r[EREC_SIDE + lf] = eside[4 * e + lf];
-      r[EREC_BC + lf] = ebc[4 * e + lf];
-      r[EREC_NBE + lf] = enbr_e[4 * e + lf];
-      r[EREC_NBLF + lf] = enbr_lf[4 * e + lf];
-      r[EREC_ACC + lf] = fslotA[efaces[4 * e + lf]] == 4 * e + lf ? 1 : 0;
-      for (int n = 0; n < ngl; n++) r[EREC_MAP + lf * ngl + n] = efmap[(4 * e + lf) * ngl + n];
-      if (ebc[4 * e + lf] > 0) {
-        // the stage kernel writes face traces into the neighbour's slot with the same face-node index
-        const int nb = enbr_e[4 * e + lf], nlf = enbr_lf[4 * e + lf];
-        for (int n = 0; n < ngl; n++)
-          if (enbr_node[(4 * e + lf) * ngl + n] != nb * P + efmap[(4 * nb + nlf) * ngl + n])
-            return fail(eng, HNUMO_ERR_INVALID, "face node orderings of neighbouring elements disagree");
-      }
-    }
-    for (int lf = 0; lf < 4; lf++)
-      for (int n = 0; n < ngl; n++) {
-        int *pf = &r[EREC_PF(ngl) + 2 * efmap[(4 * e + lf) * ngl + n]];
-        if (pf[0] < 0) pf[0] = lf * ngl + n; else if (pf[1] < 0) pf[1] = lf * ngl + n;
-        else return fail(eng, HNUMO_ERR_INVALID, "a node lies on more than two faces of its element");
-      }
-  }
-  eng->fslotA = fslotA;
-  std::vector<int> conn;
-  auto append = [&](const std::vector<int> &v) {
-    size_t off = conn.size();
-    conn.insert(conn.end(), v.begin(), v.end());
-    return off;
-  };
-  size_t o_ef = append(efaces), o_es = append(eside), o_eb = append(ebc), o_em = append(efmap);
-  size_t o_en = append(enbr_node), o_ee = append(enbr_e), o_el = append(enbr_lf), o_fl = append(fnodeL);
-  size_t o_fr = append(fnodeR), o_fe = append(fel), o_fer = append(fer);
-  size_t o_sl = append(fslotL), o_sr = append(fslotR), o_sa = append(fslotA), o_er = append(erec);
-  eng->iconn = dalloc<int>(eng, conn.size());
-  if (!eng->iconn) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed");
-  HIPCHK(hipMemcpy(eng->iconn, conn.data(), conn.size() * sizeof(int), hipMemcpyHostToDevice));
-
-  // ---- statics
-  // (+ the stage kernel's interleaved copy, basis_pd: 16-byte aligned, the counts above are even)
-  const size_t nb0 = 2 * (size_t)ngl * nq + 2 * (size_t)ngl * ngl;
-  std::vector<double> hb(nb0 + 2 * ngl * nq + ngl * ngl);
-  for (int n = 0; n < ngl; n++)
-    for (int iq = 0; iq < nq; iq++) {
-      hb[n * nq + iq] = mesh->psiq[n + ngl * iq];
-      hb[ngl * nq + n * nq + iq] = mesh->dpsiq[n + ngl * iq];
-    }
-  for (int n = 0; n < ngl; n++)
-    for (int k = 0; k < ngl; k++) {
-      hb[2 * ngl * nq + n * ngl + k] = mesh->dpsi[n + ngl * k];
-      hb[2 * ngl * nq + ngl * ngl + n * ngl + k] = mesh->psi[n + ngl * k];
-    }
-  for (int x = 0; x < ngl * nq; x++) {
-    hb[nb0 + 2 * x] = hb[x];
-    hb[nb0 + 2 * x + 1] = hb[ngl * nq + x];
-  }
-  for (int x = 0; x < ngl * ngl; x++) hb[nb0 + 2 * ngl * nq + x] = hb[2 * ngl * nq + x];
-  // the stage kernels drop the zero terms of the nodal derivative sums: psi must be the
-  // identity at the LGL nodes (it is, exactly, for the reference's nodal basis)
-  for (int n = 0; n < ngl; n++)
-    for (int k = 0; k < ngl; k++)
-      if (mesh->psi[n + ngl * k] != (n == k ? 1.0 : 0.0))
-        return fail(eng, HNUMO_ERR_INVALID, "nodal basis psi is not the identity at the LGL nodes");
-  std::vector<double> qs(QS_N * npq), ns(NS_N * npoin), fs(FS_N * FQ), fns(FN_N * FN);
-  for (size_t i = 0; i < npq; i++) {
-    qs[QS_W * npq + i] = mesh->jacq[i];
-    qs[QS_COR * npq + i] = st->coriolis_quad[i];
-    qs[QS_TW1 * npq + i] = st->tau_wind[2 * i];
-    qs[QS_TW2 * npq + i] = st->tau_wind[2 * i + 1];
-    qs[QS_GZ1 * npq + i] = st->grad_zbot_quad[2 * i];
-    qs[QS_GZ2 * npq + i] = st->grad_zbot_quad[2 * i + 1];
-    qs[QS_OOP * npq + i] = st->one_over_pbprime[i];
-    qs[QS_EX * npq + i] = mesh->ksiq_x[i];
-    qs[QS_EY * npq + i] = mesh->ksiq_y[i];
-    qs[QS_NX * npq + i] = mesh->etaq_x[i];
-    qs[QS_NY * npq + i] = mesh->etaq_y[i];
-    qs[QS_PB * npq + i] = st->pbprime[i];
-  }
-  for (size_t i = 0; i < npoin; i++) {
-    ns[NS_PB * npoin + i] = st->pbprime_df[i];
-    ns[NS_OOP * npoin + i] = st->one_over_pbprime_df[i];
-    ns[NS_MINV * npoin + i] = mesh->massinv[i];
-    ns[NS_W * npoin + i] = mesh->jac[i];
-    ns[NS_EX * npoin + i] = mesh->ksi_x[i];
-    ns[NS_EY * npoin + i] = mesh->ksi_y[i];
-    ns[NS_NX * npoin + i] = mesh->eta_x[i];
-    ns[NS_NY * npoin + i] = mesh->eta_y[i];
-    ns[NS_ZB * npoin + i] = st->zbot_df[i];
-    ns[NS_F2 * npoin + i] = st->fdt2_bcl[i];
-    ns[NS_A * npoin + i] = st->a_bcl[i];
-    ns[NS_B * npoin + i] = st->b_bcl[i];
-  }
-  for (size_t i = 0; i < FQ; i++) {
-    fs[FS_NX * FQ + i] = mesh->normal_vector_q[3 * i];
-    fs[FS_NY * FQ + i] = mesh->normal_vector_q[3 * i + 1];
-    fs[FS_W * FQ + i] = mesh->jac_faceq[i];
-    fs[FS_CL * FQ + i] = st->coeff_pbpert_L[i];
-    fs[FS_CR * FQ + i] = st->coeff_pbpert_R[i];
-    fs[FS_CLR * FQ + i] = st->coeff_pbub_LR[i];
-    fs[FS_CML * FQ + i] = st->coeff_mass_pbub_L[i];
-    fs[FS_CMR * FQ + i] = st->coeff_mass_pbub_R[i];
-    fs[FS_CMLR * FQ + i] = st->coeff_mass_pbpert_LR[i];
-    fs[FS_OOPE * FQ + i] = st->one_over_pbprime_edge[i];
-    fs[FS_PBL * FQ + i] = st->pbprime_face[2 * i];
-    fs[FS_PBR * FQ + i] = st->pbprime_face[2 * i + 1];
-    fs[FS_ZBL * FQ + i] = st->zbot_face[2 * i];
-    fs[FS_ZBR * FQ + i] = st->zbot_face[2 * i + 1];
-  }
-  for (size_t i = 0; i < FN; i++) {
-    fns[FN_NX * FN + i] = mesh->normal_vector[3 * i];
-    fns[FN_NY * FN + i] = mesh->normal_vector[3 * i + 1];
-    fns[FN_W * FN + i] = mesh->jac_face[i];
-    fns[FN_PBL * FN + i] = st->pbprime_df_face[2 * i];
-    fns[FN_PBR * FN + i] = st->pbprime_df_face[2 * i + 1];
-  }
-  // element-major statics (engine_internal.h)
-  const int Qe = nq * nq, FBLK = EF_N * nq + EFN_N * ngl;
-  std::vector<double> qsE((size_t)E * qe_stride(Qe)), nsE((size_t)E * NE_N * P), efs((size_t)E * 4 * FBLK);
-  {
-    const int qmap[QE_N] = {QS_W, QS_EX, QS_EY, QS_NX, QS_NY, QS_COR, QS_TW1, QS_TW2, QS_GZ1, QS_GZ2, QS_OOP};
-    const int nmap[NE_N] = {NS_EX, NS_EY, NS_NX, NS_NY, NS_W, NS_OOP, NS_MINV, NS_PB};
-    const int fmap_[EF_PBLQ] = {FS_NX, FS_NY, FS_W, FS_CL, FS_CR, FS_CLR, FS_CML, FS_CMR, FS_CMLR, FS_OOPE};
-    const int fnmap[EFN_N] = {FN_NX, FN_NY, FN_W, FN_PBL, FN_PBR};
-    for (int e = 0; e < E; e++) {
-      for (int c = 0; c < QE_N; c++)
-        for (int q = 0; q < Qe; q++) qsE[(size_t)e * qe_stride(Qe) + qe_pos(c, q, Qe)] = qs[qmap[c] * npq + (size_t)e * Qe + q];
-      for (int c = 0; c < NE_N; c++)
-        for (int p = 0; p < P; p++) nsE[((size_t)e * NE_N + c) * P + p] = ns[nmap[c] * npoin + (size_t)e * P + p];
-      for (int lf = 0; lf < 4; lf++) {
-        const size_t f = efaces[4 * e + lf];
-        double *b = &efs[((size_t)e * 4 + lf) * FBLK];
-        for (int c = 0; c < EF_PBLQ; c++)
-          for (int iq = 0; iq < nq; iq++) b[c * nq + iq] = fs[fmap_[c] * FQ + f * nq + iq];
-        // creat_btp_fluxes_qdf's pbl/pbr (mod_rhs_btp.F90:255-258): same products, same order
-        for (int iq = 0; iq < nq; iq++) {
-          double pl = 0.0, pr = 0.0;
-          for (int n = 0; n < ngl; n++) {
-            pl = pl + hb[n * nq + iq] * fns[FN_PBL * FN + f * ngl + n];
-            pr = pr + hb[n * nq + iq] * fns[FN_PBR * FN + f * ngl + n];
-          }
-          b[EF_PBLQ * nq + iq] = pl;
-          b[EF_PBRQ * nq + iq] = pr;
-        }
-        for (int c = 0; c < EFN_N; c++)
-          for (int n = 0; n < ngl; n++) b[EF_N * nq + c * ngl + n] = fns[fnmap[c] * FN + f * ngl + n];
-      }
-    }
-  }
-  eng->ssprk_a.assign(st->ssprk_a, st->ssprk_a + 3 * par->kstages);
-  eng->ssprk_beta.assign(st->ssprk_beta, st->ssprk_beta + par->kstages);
-
-  eng->basis = dalloc<double>(eng, hb.size());
-  eng->qstat = dalloc<double>(eng, qs.size());
-  eng->nstat = dalloc<double>(eng, ns.size());
-  eng->fstat = dalloc<double>(eng, fs.size());
-  eng->fnstat = dalloc<double>(eng, fns.size());
-  eng->qstatE = dalloc<double>(eng, qsE.size());
-  eng->nstatE = dalloc<double>(eng, nsE.size());
-  eng->efstat = dalloc<double>(eng, efs.size());
-  eng->ecoef = dalloc<double>(eng, (size_t)E * eco_stride(Qe, P));
-  eng->efcoef = dalloc<double>(eng, (size_t)E * 4 * (4 * nq + 10 * ngl));
-  eng->alpha = dalloc<double>(eng, L);
-  eng->tau_wind = dalloc<double>(eng, 2 * npq);
-  const size_t n3 = 3 * npoin * L;
-  eng->q = dalloc<double>(eng, n3); eng->qp = dalloc<double>(eng, n3); eng->qb = dalloc<double>(eng, 4 * npoin);
-  eng->q2 = dalloc<double>(eng, n3); eng->qp2 = dalloc<double>(eng, n3); eng->qbp = dalloc<double>(eng, 4 * npoin);
-  eng->qf = dalloc<double>(eng, 6 * FN * L); eng->qf2 = dalloc<double>(eng, 6 * FN * L);
-  eng->qfa = dalloc<double>(eng, 6 * FN * L);
-  eng->dpp2 = dalloc<double>(eng, npoin * L);
-  for (int i = 0; i < 4; i++) eng->qbuf[i] = dalloc<double>(eng, 4 * npoin);
-  // trace buffers: element slots [4E], then (processor-face halo) NS send + NS receive slots
-  for (int i = 0; i < 2; i++) eng->gtrace[i] = dalloc<double>(eng, (4 * (size_t)E + 2 * (size_t)eng->NS) * 8 * ngl);
-  eng->qcoef = dalloc<double>(eng, QC_N * npq); eng->ncoef = dalloc<double>(eng, NC_N * npoin);
-  eng->fcoef = dalloc<double>(eng, FC_N * FQ); eng->fncoef = dalloc<double>(eng, 10 * FN);
-  eng->dpp_graduv = dalloc<double>(eng, 4 * npoin * L); eng->dpprime_visc = dalloc<double>(eng, npoin * L);
-  eng->gdpp_face = dalloc<double>(eng, 10 * FN * L);
-  eng->qacc = dalloc<double>(eng, QA_N * npq); eng->facc = dalloc<double>(eng, FA_N * 4 * (size_t)E * nq);
-  eng->nacc = dalloc<double>(eng, NA_N * npoin); eng->gfacc = dalloc<double>(eng, 8 * 4 * (size_t)E * ngl);
-  eng->tau_wind_ave = dalloc<double>(eng, 2 * npq);
-  eng->slmf = dalloc<double>(eng, 2 * npq); eng->slmf_face = dalloc<double>(eng, 2 * FQ);
-  eng->dpp = dalloc<double>(eng, npoin * L);
-  eng->fmass = dalloc<double>(eng, FQ * L); eng->fcons = dalloc<double>(eng, FQ * L);
-  eng->momL = dalloc<double>(eng, 4 * (size_t)E * 2 * nq * L);  // [slot][L][2][NQ] (MSLOT)
-  eng->momR = nullptr;
-  eng->lapf = dalloc<double>(eng, 4 * (size_t)E * 2 * ngl * L);  // [slot][L][2][NGL]
-  if (par->method_visc == 1) {  // quad-point LDG (kernels_lapq.hip)
-    eng->lapq_on = true;
-    eng->dpq = dalloc<double>(eng, npq * L);
-    eng->lq_flux = dalloc<double>(eng, 4 * npq * L);
-    eng->lapq = dalloc<double>(eng, 2 * npoin * L);
-    std::vector<int> fq(2 * FQ, -1);
-    for (int s = 0; s < 2; s++) {
-      const int32_t *imq = s == 0 ? mesh->imapl_q : mesh->imapr_q;
-      for (int f = 0; f < F; f++)
-        for (int iq = 0; iq < nq; iq++) {
-          const int i = imq[3 * (iq + nq * f)] - 1, j = imq[3 * (iq + nq * f) + 1] - 1;
-          if (s == 1 && mesh->face[8 * f + 7] <= 0) continue;
-          if (i < 0 || i >= nq || j < 0 || j >= nq) return fail(eng, HNUMO_ERR_INVALID, "imapl_q/imapr_q out of range");
-          fq[s * FQ + (size_t)f * nq + iq] = j * nq + i;
-        }
-    }
-    eng->fqLR = dalloc<int>(eng, 2 * FQ);
-    if (eng->fqLR) HIPCHK(hipMemcpy(eng->fqLR, fq.data(), fq.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  eng->rhs = dalloc<double>(eng, 3 * npoin);
-  eng->neg_flag = dalloc<int>(eng, 1);
-  if (const char *ge = env_knob(eng, "HNUMO_GRAPH", false)) eng->graph_env = ge[0] == '0' ? 0 : ge[0] == '1' ? 1 : -1;
-  if (const char *sm = env_knob(eng, "HNUMO_SUMMATION", false)) {
-    if (!strcmp(sm, "reference"))
-      eng->summation = HNUMO_SUM_REFERENCE;
-    else if (!strcmp(sm, "factored"))
-      eng->summation = HNUMO_SUM_FACTORED;
-    else
-      return fail(eng, HNUMO_ERR_INVALID, std::string("HNUMO_SUMMATION=") + sm + ": only 'reference' or 'factored'");
-  }
-  if (HNUMO_DIAG)  // (diagnostics builds only; see engine_internal.h)
-    if (const char *sd = env_knob(eng, "HNUMO_STAGE_DBG")) eng->stage_dbg = atoi(sd);
-  if (const char *fz = env_knob(eng, "HNUMO_FUSE")) eng->no_fuse = fz[0] == '0';
-  // (bit 1 drops a required stream dependency -- wrong results, timing only: diagnostics builds)
-  if (HNUMO_DIAG)
-    if (const char *sd = env_knob(eng, "HNUMO_SCHED_DBG")) eng->sched_dbg = atoi(sd);
-  // per-stage kernel arena: on meshes that take several residency rounds per stage, the arena
-  // sized for 4 workgroups per CU (1-row term chunks) -- 1.566 -> 1.517 ms per stage at C4
-  // (tools/ab_env.py, round 2); small meshes keep the 3-per-CU arena
-  // large meshes: the LEAN 5-per-CU arena (C4: 1.331 ms per stage against 1.409 for the 4-per-CU
-  // one with 2-row term chunks and 1.501 for round 2's, profiles/r03f)
-  eng->stage_nb = eng->nelem_owned >= 2048 ? 5 : 0;
-  if (const char *sn = env_knob(eng, "HNUMO_STAGE_NB")) eng->stage_nb = atoi(sn);
-  eng->bcl_big = eng->nelem_owned >= 2048;
-  if (const char *bb = env_knob(eng, "HNUMO_BCL_BIG")) eng->bcl_big = bb[0] == '1';
-  if (const char *az = env_knob(eng, "HNUMO_ACC_ZERO")) eng->acc_zero = az[0] == '1';
-  {
-    const char *qv = env_knob(eng, "HNUMO_QPQ");
-    if (par->botfr && !(qv && atoi(qv) == 0)) eng->qpq = dalloc<double>(eng, (size_t)E * 3 * eng->nq * eng->nq);
-  }
-  if (const char *sp = HNUMO_DIAG ? env_knob(eng, "HNUMO_STAGE_PROF") : nullptr)
-    if (sp[0] == '1') eng->stage_prof = dalloc<unsigned long long>(eng, (size_t)eng->nelem * 32);
-  if (eng->face_halo) {
-    eng->rank = halo->rank;
-    eng->nranks = halo->nranks;
-    const int NS = eng->NS;
-    // trace source slot of every element face; boundary / interior element lists
-    std::vector<int> tsrc(4 * (size_t)E), elB, elI;
-    for (int e = 0; e < E; e++) {
-      bool bnd = false;
-      for (int lf = 0; lf < 4; lf++) {
-        const int f = efaces[4 * e + lf];
-        const bool proc = ebc[4 * e + lf] == 0;
-        tsrc[4 * e + lf] = proc ? 4 * E + NS + face_slot[f] : 4 * e + lf;
-        bnd |= proc;
-      }
-      (bnd ? elB : elI).push_back(e);
-    }
-    eng->nB = (int)elB.size();
-    eng->nI = (int)elI.size();
-    int *d_tsrc = dalloc<int>(eng, tsrc.size());
-    eng->d_sface = dalloc<int>(eng, NS);
-    eng->d_elB = dalloc<int>(eng, elB.size());
-    eng->d_elI = dalloc<int>(eng, elI.size());
-    eng->cdef = dalloc<double>(eng, 4 * FQ * L);
-    eng->bx_per_max = (size_t)L * std::max({5 * ngl, 2 * nq, eng->lapq_on ? 4 * nq : 0});
-    eng->bx_sbuf = dalloc<double>(eng, eng->bx_per_max * NS);
-    eng->bx_rbuf = dalloc<double>(eng, eng->bx_per_max * NS);
-    if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (halo buffers)");
-    HIPCHK(hipMemcpy(d_tsrc, tsrc.data(), tsrc.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (NS) HIPCHK(hipMemcpy(eng->d_sface, sface.data(), NS * sizeof(int), hipMemcpyHostToDevice));
-    if (eng->nB) HIPCHK(hipMemcpy(eng->d_elB, elB.data(), elB.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (eng->nI) HIPCHK(hipMemcpy(eng->d_elI, elI.data(), elI.size() * sizeof(int), hipMemcpyHostToDevice));
-    eng->m.etsrc = d_tsrc;
-    // the boundary elements and their transport are the critical path of the stage chain:
-    // their stream gets the highest priority, so their workgroups dispatch ahead of the
-    // interior launch's
-    int prio_lo = 0, prio_hi = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    HIPCHK(hipStreamCreateWithPriority(&eng->stream2, hipStreamNonBlocking, prio_hi));
-    for (hipEvent_t *ev : {&eng->ev_fork, &eng->ev_join, &eng->ev_I, &eng->ev_B[0], &eng->ev_B[1], &eng->ev_tsent,
-                           &eng->ev_bpacked, &eng->ev_bdone})
-      HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    for (hipEvent_t *ev : {&eng->ev_Is, &eng->ev_Bs[0], &eng->ev_Bs[1]}) HIPCHK(hipEventCreate(ev));
-    if (halo->comm_id) {  // RCCL point-to-point over xGMI
-      ncclUniqueId id;
-      static_assert(sizeof(ncclUniqueId) == 128, "RCCL unique id size");
-      std::memcpy(&id, halo->comm_id, sizeof(id));
-      ncclResult_t nr = ncclCommInitRank(&eng->comm, halo->nranks, id, halo->rank);
-      if (nr != ncclSuccess) return fail(eng, HNUMO_ERR_DEVICE, std::string("ncclCommInitRank: ") + ncclGetErrorString(nr));
-      eng->comm_mode = 2;
-    }
-  } else if (halo && halo->nranks > 1) {
-    eng->rank = halo->rank;
-    eng->nranks = halo->nranks;
-    size_t os = 0, orr = 0;
-    const size_t per_max = (size_t)P * std::max(4, 3 * L);
-    for (int k = 0; k < halo->num_nbh; k++) {
-      Neighbour nb;
-      nb.rank = halo->nbh_proc[k];
-      nb.nsend = halo->num_ghost_send ? halo->num_ghost_send[k] : 0;
-      nb.nrecv = halo->num_ghost_recv ? halo->num_ghost_recv[k] : 0;
-      if (nb.rank < 0 || nb.rank >= halo->nranks || nb.rank == halo->rank)
-        return fail(eng, HNUMO_ERR_INVALID, "bad neighbour rank");
-      for (const auto &pn : eng->nbh)
-        if (pn.rank == nb.rank) return fail(eng, HNUMO_ERR_INVALID, "a neighbour rank is listed twice");
-      std::vector<int> snd(nb.nsend), rcv(nb.nrecv);
-      for (int i = 0; i < nb.nsend; i++) {
-        snd[i] = halo->ghost_send[os + i] - 1;
-        if (snd[i] < 0 || snd[i] >= eng->nelem_owned) return fail(eng, HNUMO_ERR_INVALID, "ghost_send must list owned elements");
-      }
-      for (int i = 0; i < nb.nrecv; i++) {
-        rcv[i] = halo->ghost_recv[orr + i] - 1;
-        if (rcv[i] < eng->nelem_owned || rcv[i] >= E) return fail(eng, HNUMO_ERR_INVALID, "ghost_recv must list ghost elements");
-      }
-      os += nb.nsend;
-      orr += nb.nrecv;
-      nb.d_send = dalloc<int>(eng, nb.nsend);
-      nb.d_recv = dalloc<int>(eng, nb.nrecv);
-      nb.sbuf = dalloc<double>(eng, nb.nsend * per_max);
-      nb.rbuf = dalloc<double>(eng, nb.nrecv * per_max);
-      if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (halo buffers)");
-      if (nb.nsend) HIPCHK(hipMemcpy(nb.d_send, snd.data(), nb.nsend * sizeof(int), hipMemcpyHostToDevice));
-      if (nb.nrecv) HIPCHK(hipMemcpy(nb.d_recv, rcv.data(), nb.nrecv * sizeof(int), hipMemcpyHostToDevice));
-      eng->nbh.push_back(nb);
-    }
-    if (halo->comm_id) {  // RCCL point-to-point over xGMI
-      ncclUniqueId id;
-      static_assert(sizeof(ncclUniqueId) == 128, "RCCL unique id size");
-      std::memcpy(&id, halo->comm_id, sizeof(id));
-      ncclResult_t nr = ncclCommInitRank(&eng->comm, halo->nranks, id, halo->rank);
-      if (nr != ncclSuccess) return fail(eng, HNUMO_ERR_DEVICE, std::string("ncclCommInitRank: ") + ncclGetErrorString(nr));
-      eng->comm_mode = 2;
-    }
-  }
-  if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (out of device memory?)");
-  HIPCHK(hipHostMalloc((void **)&eng->h_neg, sizeof(int)));
-  HIPCHK(hipMemcpy(eng->basis, hb.data(), hb.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->qstat, qs.data(), qs.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->nstat, ns.data(), ns.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->fstat, fs.data(), fs.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->fnstat, fns.data(), fns.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->qstatE, qsE.data(), qsE.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->nstatE, nsE.data(), nsE.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->efstat, efs.data(), efs.size() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->alpha, st->alpha, L * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eng->tau_wind, st->tau_wind, 2 * npq * 8, hipMemcpyHostToDevice));
-
-  DevMesh &m = eng->m;
-  m.nelem = E; m.npoin = (int)npoin; m.npoin_q = (int)npq; m.nface = F; m.ngl = ngl; m.nq = nq; m.L = L;
-  m.efaces = eng->iconn + o_ef; m.eside = eng->iconn + o_es; m.ebc = eng->iconn + o_eb; m.efmap = eng->iconn + o_em;
-  m.enbr_node = eng->iconn + o_en; m.enbr_e = eng->iconn + o_ee; m.enbr_lf = eng->iconn + o_el;
-  m.fnodeL = eng->iconn + o_fl; m.fnodeR = eng->iconn + o_fr; m.fel = eng->iconn + o_fe; m.fer = eng->iconn + o_fer;
-  m.fslotL = eng->iconn + o_sl; m.fslotR = eng->iconn + o_sr; m.fslotA = eng->iconn + o_sa;
-  m.erec = eng->iconn + o_er;
-  m.qstatE = eng->qstatE; m.nstatE = eng->nstatE; m.efstat = eng->efstat;
-  m.basis = eng->basis; m.basis_pd = eng->basis + nb0; m.qstat = eng->qstat; m.nstat = eng->nstat; m.fstat = eng->fstat; m.fnstat = eng->fnstat;
-  m.alpha = eng->alpha;
-  m.gravity = par->gravity; m.cd = par->cd_mlswe; m.visc = par->visc_mlswe; m.dt = par->dt; m.dt_btp = par->dt_btp;
-  m.botfr = par->botfr;
-  m.ad = par->ad_mlswe; m.max_shear_dz = par->max_shear_dz; m.shear_corr = par->shear_corrector;
-  m.runflag = eng->neg_flag;
-  eng->steps_done = dalloc<unsigned>(eng, 1);
-  m.steps_done = eng->steps_done;
-  HIPCHK(hipHostMalloc((void **)&eng->h_steps, sizeof(unsigned)));
-
-  // persistent sub-cycle: stage tables for the two sub-cycles of a step and the residency check
-  if (supported_ngl(ngl) && eng->K <= 8) {
-    eng->epoch = dalloc<unsigned long long>(eng, 1);
-    eng->qsv = dalloc<double>(eng, (size_t)E * 8 * ngl * ngl);
-    eng->sub_done = dalloc<unsigned>(eng, 1);
-    eng->sub_arrive = dalloc<unsigned>(eng, 1);
-    eng->dbg_abort_epoch = dalloc<unsigned long long>(eng, 1);
-    if (eng->dbg_abort_epoch) HIPCHK(hipMemset(eng->dbg_abort_epoch, 0xff, sizeof(unsigned long long)));  // never
-    for (int b = 0; b < 2; b++) eng->gtr[b] = dalloc<TraceGranule>(eng, (size_t)E * 32 * ngl);
-    const char *pe = env_knob(eng, "HNUMO_PERSISTENT", false);
-    const bool persist_on = !(pe && pe[0] == '0');
-    if (persist_on) {
-      if (const char *pp = env_knob(eng, "HNUMO_PERSIST_LDS_PAD")) eng->persist_pad = std::max(0, atoi(pp));
-      // HNUMO_PERSIST_GUARD: 0 none (the in-launch rendezvous alone), 'estimate', 'trial', 1 both
-      if (const char *pg = env_knob(eng, "HNUMO_PERSIST_GUARD"))
-        eng->persist_guard = pg[0] == '0' ? 0 : pg[0] == 'e' ? 1 : pg[0] == 't' ? 2 : 3;
-      int ncu = 0;
-      HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, eng->device));
-      DISPATCH(eng, occupancy(eng, ncu));
-      // (HNUMO_PERSIST_PERM=0: the identity) workgroup b runs on CU b % ncu (the dispatcher's round-robin; blocks b,
-      // b + ncu, b + 2 ncu share a CU), so with E/ncu not whole some CUs hold one element more; the
-      // elements with a physical-boundary face (more work: ghost states, wall fluxes) go to the CUs
-      // holding fewer, the others fill the rest in order.  Same arithmetic per element, same bits
-      // (dg25L3: 16 us less sub-cycle time per step in 3 interleaved pairs, profiles/r05x).
-      const char *pm = env_knob(eng, "HNUMO_PERSIST_PERM");
-      if (!(pm && pm[0] == '0') && ncu > 0 && E % ncu && eng->nranks == 1 && !eng->face_halo && eng->comm_mode == 0 &&
-          eng->nelem_owned == E) {
-        const int nheavy = E % ncu;  // CUs k < nheavy hold one block more
-        // (measured, not kept: also grouping by XCD -- blocks b and b + 8 share one, so group b % 8
-        // took the (b % 8)-th strip of consecutive element ids: 2268 against 2224 us of sub-cycle per
-        // step, profiles/r05z)
-        std::vector<int> bnd, inr, perm(E);
-        for (int el = 0; el < E; el++) {
-          bool b = false;
-          for (int lf = 0; lf < 4; lf++) b = b || ebc[4 * el + lf] < 0;
-          (b ? bnd : inr).push_back(el);
-        }
-        size_t ib = 0, ii = 0;
-        // (measured, not kept: a CU's blocks on consecutive element ids -- neighbours sharing a CU --
-        // 2357 against 2208 us of sub-cycle per step, profiles/r05ac)
-        for (int b = 0; b < E; b++) {
-          const bool light = (b % ncu) >= nheavy;
-          perm[b] = (light && ib < bnd.size()) ? bnd[ib++] : (ii < inr.size() ? inr[ii++] : bnd[ib++]);
-        }
-        eng->d_eperm = dalloc<int>(eng, E);
-        if (eng->d_eperm) HIPCHK(hipMemcpy(eng->d_eperm, perm.data(), E * sizeof(int), hipMemcpyHostToDevice));
-        // the element kernels of the step (625 blocks at dg25 too: the same CUs hold one block more)
-        const char *pg = env_knob(eng, "HNUMO_GLUE_PERM");
-        if (!(pg && pg[0] == '0')) eng->m.eperm = eng->d_eperm;
-      }
-    }
-    // the stage tables copy eng->m: built after the placement above, so every DevMesh copy (these,
-    // the per-stage tables of stage_table at run time) carries the same eperm
-    const double *qps[2] = {eng->qp, eng->qp2};
-    for (int v = 0; v < 2; v++) {
-      std::vector<StageArgs> st;
-      (void)stage_table(eng, qps[v], st);
-      st.front().qb_in = eng->qb;                        // the step-start state (launch_subcycle)
-      st.front().self_trace = 1;                         // stage 0 publishes its input traces
-      st.back().qb_out = v == 0 ? eng->qbp : eng->qb;    // predictor / corrector result
-      eng->d_stages[v] = dalloc<StageArgs>(eng, st.size());
-      if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (stage tables)");
-      HIPCHK(hipMemcpy(eng->d_stages[v], st.data(), st.size() * sizeof(StageArgs), hipMemcpyHostToDevice));
-    }
-    if (persist_on) {
-      // the trial launches: what the dispatcher does, not what the estimate says, decides
-      for (int sm = 0; sm < 2 && (eng->persist_guard & 2); sm++) {
-        if (!eng->persistent_ok[sm] || eng->comm_mode != 0 || eng->nranks != 1) continue;
-        HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-        DISPATCH(eng, probe(eng, sm));
-        HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-        HIPCHK(hipStreamSynchronize(eng->stream));
-        HIPCHK(hipGetLastError());
-        eng->probe_ok[sm] = (*eng->h_neg & RUN_ABORT) ? 0 : 1;
-        if (!eng->probe_ok[sm]) eng->persistent_ok[sm] = false;
-        HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-      }
-    }
-  }
+  // every descriptor error is reported here, before any device call
+  SetupPlan pl;
+  if (int rc = build_setup_plan(mesh, st, par, halo, pl, eng->err)) return rc;
+  adopt_plan(eng, mesh, st, par, halo, pl);
+  int ncu = 0;
+  Knobs k;
+  if (int rc = open_device(eng, &ncu)) return rc;
+  if (int rc = read_knobs(eng, ncu, k)) return rc;
+  if (int rc = create_buffers(eng, pl, st, k)) return rc;
+  if (int rc = create_halo(eng, pl, halo)) return rc;
+  fill_devmesh(eng, pl);
+  if (int rc = setup_persistent(eng, pl, k, ncu)) return rc;
   // tau_wind_ave = (N_btp times tau_wind summed) / N_btp (mod_rk_mlswe.F90:148) is constant: formed
   // once here (btp_finalize_kernel also re-forms it after every per-stage sub-cycle)
   hipLaunchKernelGGL(btp_finalize_kernel, dim3(256), dim3(256), 0, eng->stream, eng->qacc, eng->facc, eng->nacc,
-                     eng->gfacc, eng->tau_wind_ave, eng->tau_wind, (int)npq, 0, 0, 0, par->N_btp, 1.0, nullptr,
+                     eng->gfacc, eng->tau_wind_ave, eng->tau_wind, eng->npq, 0, 0, 0, par->N_btp, 1.0, nullptr,
                      nullptr, 0);
   HIPCHK(hipDeviceSynchronize());
   return HNUMO_OK;
