@@ -4,8 +4,9 @@
 // (ti_rk_bcl.F90:9-87) with the kernels of kernels_btp.hip / kernels_bcl.hip.  A whole
 // baroclinic step (2 barotropic sub-cycles = 2*N_btp*kstages fused stage kernels plus
 // ~20 baroclinic kernels) is captured once into a hipGraph and replayed.  The run diagnostics of
-// the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) are plain
-// launches on the same stream between replays.
+// the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) and the
+// online flow statistics (kernels_stats.hip: hnumo_stats_*) are plain launches on the same stream
+// between replays.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -28,6 +29,7 @@
 #include "kernels_btp.hip"
 #include "kernels_lapq.hip"
 #include "kernels_diag.hip"
+#include "kernels_stats.hip"
 
 using namespace hnumo;
 
@@ -187,6 +189,14 @@ struct hnumo_engine {
   const double *diag_w = nullptr;
   double *h_diag = nullptr;                  // pinned copy of diag_out
   double diag_min_dx = 1e16, diag_min_dy = 1e16;
+  // online flow statistics (kernels_stats.hip; hnumo_stats_begin .. hnumo_stats_end): the running
+  // sums [L][2][npoin] pairs, the element partials [2L][ne] and the two buffers of the tree's
+  // passes, the series [capacity][L][2]; samples taken, series entries held, successful steps
+  // since begin (every > 0: the engine samples after every every-th one)
+  bool stats_on = false;
+  double *st_sums = nullptr, *st_part = nullptr, *st_tree[2] = {nullptr, nullptr}, *st_series = nullptr;
+  int st_every = 0, st_cap = 0, st_count = 0;
+  int64_t st_nsamples = 0, st_steps = 0;
 };
 
 // the per-kernel breakdown's mark after a launch on the engine stream (no-op outside
@@ -1331,6 +1341,8 @@ int hnumo_overrides(const hnumo_engine *eng, char *out, int64_t len) {
 
 const char *hnumo_last_error(const hnumo_engine *eng) { return eng ? eng->err.c_str() : "null engine"; }
 
+static void stats_free(hnumo_engine *eng);
+
 void hnumo_engine_destroy(hnumo_engine *eng) {
   if (!eng) return;
   (void)hipSetDevice(eng->device);
@@ -1340,6 +1352,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   if (eng->h_neg) (void)hipHostFree(eng->h_neg);
   if (eng->h_steps) (void)hipHostFree(eng->h_steps);
   if (eng->h_diag) (void)hipHostFree(eng->h_diag);
+  stats_free(eng);
   if (eng->stream && eng->own_stream) (void)hipStreamDestroy(eng->stream);
   if (LocalGroup *g = eng->group) {
     // the destroyed engine cannot take part in exchanges any more; the last one out frees
@@ -1567,6 +1580,10 @@ static int component_transport_check(hnumo_engine *eng) {
   return 0;
 }
 
+// the flow statistics' sample after a successful step (hnumo_stats_begin with every >= 1; a no-op
+// otherwise): after run_steps returned 0, so a step redone on per-stage launches is sampled once
+static int stats_after_step(hnumo_engine *eng);
+
 int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime_df) {
   if (!eng) return HNUMO_ERR_INVALID;
   if (int rc = component_transport_check(eng)) return rc;
@@ -1578,8 +1595,8 @@ int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qpri
   }
   int rc = run_steps(eng, 1);
   if (rc) return rc;
-  if (!eng->resident) return download_state(eng, q_df, qb_df, qprime_df);
-  return 0;
+  if (!eng->resident && (rc = download_state(eng, q_df, qb_df, qprime_df))) return rc;
+  return stats_after_step(eng);
 }
 
 int hnumo_set_resident(hnumo_engine *eng, int on) {
@@ -1815,6 +1832,223 @@ int hnumo_layer_fields(hnumo_engine *eng, double *out5, int64_t n) {
   if (err == hipSuccess) err = hipGetLastError();
   (void)hipFree(d);
   HIPCHK(err);
+  return HNUMO_OK;
+}
+
+// ------------------------------------------------------------------ online flow statistics
+// (kernels_stats.hip; plain launches on the engine stream after the step, outside the captured
+// step: the step's launches, graph and bits are the same with statistics on or off)
+static void stats_free(hnumo_engine *eng) {
+  for (double **p : {&eng->st_sums, &eng->st_part, &eng->st_tree[0], &eng->st_tree[1], &eng->st_series}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  eng->stats_on = false;
+  eng->st_every = eng->st_cap = eng->st_count = 0;
+  eng->st_nsamples = eng->st_steps = 0;
+}
+
+static size_t stats_nsums(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
+
+int hnumo_stats_begin(hnumo_engine *eng, int32_t every, int32_t series_capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (every < 0 || series_capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: every and series_capacity must be >= 0, got " +
+                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  if (eng->L < 1 || eng->L > MAXL || eng->ngl < 2 || eng->ngl * eng->ngl > ST_BS)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: unsupported nlayers or ngl");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
+  stats_free(eng);
+  const int L = eng->L, ne = eng->nelem_owned;
+  auto alloc = [&](double **p, size_t n) { return hipMalloc((void **)p, (n ? n : 1) * sizeof(double)) == hipSuccess; };
+  bool ok = alloc(&eng->st_sums, stats_nsums(eng));
+  if (series_capacity > 0) {
+    const size_t nch = ((size_t)ne + ST_CHUNK - 1) / ST_CHUNK;
+    ok = ok && alloc(&eng->st_part, (size_t)2 * L * ne) && alloc(&eng->st_tree[0], 2 * L * nch) &&
+         alloc(&eng->st_tree[1], 2 * L * ((nch + ST_CHUNK - 1) / ST_CHUNK)) &&
+         alloc(&eng->st_series, (size_t)2 * L * series_capacity);
+  }
+  if (!ok) {
+    stats_free(eng);
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_stats_begin: device allocation failed");
+  }
+  HIPCHK(hipMemsetAsync(eng->st_sums, 0, stats_nsums(eng) * sizeof(double), eng->stream));
+  if (series_capacity > 0)
+    HIPCHK(hipMemsetAsync(eng->st_series, 0, (size_t)2 * L * series_capacity * sizeof(double), eng->stream));
+  eng->st_every = every;
+  eng->st_cap = series_capacity;
+  eng->stats_on = true;
+  return HNUMO_OK;
+}
+
+int hnumo_stats_end(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats_on) return HNUMO_OK;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  stats_free(eng);
+  return HNUMO_OK;
+}
+
+#define STATS_LAUNCH(L_)                                                                                       \
+  do {                                                                                                         \
+    if (series)                                                                                                \
+      hipLaunchKernelGGL((stats_accumulate_kernel<L_, true>), dim3(nb), dim3(ST_BS), 0, eng->stream, a);       \
+    else                                                                                                       \
+      hipLaunchKernelGGL((stats_accumulate_kernel<L_, false>), dim3(nb), dim3(ST_BS), 0, eng->stream, a);      \
+  } while (0)
+
+// one sample of the state on the device, ordered after what is on the engine stream; no copy back
+static int stats_sample(hnumo_engine *eng, const char *who) {
+  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_stats_begin first");
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  const bool series = eng->st_cap > 0;
+  if (series && eng->st_count >= eng->st_cap)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series is full (" + std::to_string(eng->st_cap) +
+                                            " samples): nothing accumulated; read it with clear = 1");
+  const int L = eng->L, ne = eng->nelem_owned, EPB = ST_BS / eng->P;
+  if (ne > 0) {
+    StatsArgs a{};
+    a.q = eng->q;
+    a.alpha = eng->alpha;
+    a.w = eng->nstat + (size_t)NS_W * eng->npoin;
+    a.sums = (double2 *)eng->st_sums;
+    a.part = eng->st_part;
+    a.gravity = eng->p.gravity;
+    a.npoin = eng->npoin;
+    a.ne = ne;
+    a.ngl = eng->ngl;
+    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    switch (L) {
+      case 1: STATS_LAUNCH(1); break;
+      case 2: STATS_LAUNCH(2); break;
+      default: STATS_LAUNCH(3); break;
+    }
+    if (series) {
+      // the tree: passes over aligned chunks until one value per row is left, which the last pass
+      // writes into the sample's slot of the series
+      const double *in = eng->st_part;
+      int n = ne, pass = 0;
+      for (;;) {
+        const int nch = (n + ST_CHUNK - 1) / ST_CHUNK;
+        const bool last = nch == 1;
+        double *out = last ? eng->st_series + (size_t)eng->st_count * 2 * L : eng->st_tree[pass & 1];
+        hipLaunchKernelGGL(stats_tree_kernel, dim3(nch, 2 * L), dim3(ST_BS), 0, eng->stream, in, n, out, last ? 1 : nch);
+        if (last) break;
+        in = out;
+        n = nch;
+        pass++;
+      }
+    }
+    HIPCHK(hipGetLastError());
+  }
+  if (series) eng->st_count++;
+  eng->st_nsamples++;
+  return HNUMO_OK;
+}
+
+static int stats_after_step(hnumo_engine *eng) {
+  if (!eng->stats_on || eng->st_every <= 0) return 0;
+  if (++eng->st_steps % eng->st_every) return 0;
+  return stats_sample(eng, "flow statistics after the step (the step itself succeeded)");
+}
+
+int hnumo_stats_accumulate(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return stats_sample(eng, "hnumo_stats_accumulate");
+}
+
+// the sums between the device layout [L][2][npoin][2] and the caller's (4,npoin,L)
+int hnumo_stats_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: call hnumo_stats_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: out is NULL");
+  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  HIPCHK(hipMemcpyAsync(raw.data(), eng->st_sums, want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  for (int k = 0; k < eng->L; k++)
+    for (int p = 0; p < 2; p++)
+      for (size_t I = 0; I < npoin; I++)
+        for (int j = 0; j < 2; j++) out[4 * (I + npoin * k) + 2 * p + j] = raw[2 * st_pair(k, p, I, npoin) + j];
+  if (nsamples) *nsamples = eng->st_nsamples;
+  return HNUMO_OK;
+}
+
+int hnumo_stats_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: call hnumo_stats_begin first");
+  if (!in) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: in is NULL");
+  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: nsamples must be >= 0");
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  for (int k = 0; k < eng->L; k++)
+    for (int p = 0; p < 2; p++)
+      for (size_t I = 0; I < npoin; I++)
+        for (int j = 0; j < 2; j++) raw[2 * st_pair(k, p, I, npoin) + j] = in[4 * (I + npoin * k) + 2 * p + j];
+  HIPCHK(hipMemcpyAsync(eng->st_sums, raw.data(), want * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  eng->st_nsamples = nsamples;
+  return HNUMO_OK;
+}
+
+int hnumo_stats_fields(hnumo_engine *eng, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: call hnumo_stats_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: out is NULL");
+  const int64_t want = 5 * (int64_t)eng->npoin * eng->L;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: n must be 5*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  if (eng->st_nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: no samples yet");
+  HIPCHK(hipSetDevice(eng->device));
+  double *d = nullptr;
+  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
+  const size_t npoin = (size_t)eng->npoin, nown = (size_t)eng->nelem_owned * eng->P;
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((npoin + ST_BS - 1) / ST_BS, 4096));
+  const double2 *s = (const double2 *)eng->st_sums;
+  const double ns = (double)eng->st_nsamples;
+  switch (eng->L) {
+    case 1: hipLaunchKernelGGL(stats_fields_kernel<1>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d); break;
+    case 2: hipLaunchKernelGGL(stats_fields_kernel<2>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d); break;
+    default: hipLaunchKernelGGL(stats_fields_kernel<3>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d); break;
+  }
+  hipError_t err = hipMemcpyAsync(out, d, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(eng->stream);
+  if (err == hipSuccess) err = hipGetLastError();
+  (void)hipFree(d);
+  HIPCHK(err);
+  return HNUMO_OK;
+}
+
+int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_series: call hnumo_stats_begin first");
+  const int64_t want = 2 * (int64_t)eng->L * eng->st_count;
+  if (n < 0 || (out && n < want))
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_series: out holds n = " + std::to_string(n) +
+                                            " values, the series has 2*nlayers*count = " + std::to_string(want));
+  HIPCHK(hipSetDevice(eng->device));
+  if (out && want > 0) {
+    HIPCHK(hipMemcpyAsync(out, eng->st_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    HIPCHK(hipStreamSynchronize(eng->stream));
+    HIPCHK(hipGetLastError());
+  }
+  if (count) *count = eng->st_count;
+  // (the next sample's slot is written after this copy on the same stream)
+  if (clear && out) eng->st_count = 0;
   return HNUMO_OK;
 }
 
@@ -2191,6 +2425,11 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
   for (auto &t : th) t.join();
   for (int i = 0; i < n; i++)
     if (rc[i]) return rc[i];
+  // (the step of every engine succeeded: the flow statistics' samples, each on its engine's stream)
+  for (int i = 0; i < n; i++) {
+    (void)hipSetDevice(engines[i]->device);
+    if (int r = stats_after_step(engines[i])) return r;
+  }
   return 0;
 }
 

@@ -281,7 +281,7 @@ def restart_state(case, path):
 # ------------------------------------------------------------------ the time loop
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
-              time_scale=1.0, out=None, device_diagnostics=False):
+              time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
@@ -293,7 +293,14 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     bits -- instead of from the synced copy; without dump_data the final report does too, so no
     sync is issued for reporting (the one before the return fills the returned arrays).  The
     initial report and the initial masses stay on the host.  A stepper without `diagnostics`
-    reports on the host as with False."""
+    reports on the host as with False.
+
+    flow_stats: a hnumo.flowstats.DeviceFlowStats or HostFlowStats; after every stats_every-th step
+    of this loop it gets add(q).  The device object samples the engine's state where it lives (q is
+    ignored, no sync); the host object reads the host arrays, which a resident stepper syncs for it
+    first.  None: nothing changes."""
+    if flow_stats is not None and int(stats_every) < 1:
+        raise ValueError("stats_every must be >= 1")
     S = case.scalars
     out = out or sys.stdout
     dt = S["dt"]
@@ -344,11 +351,17 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     if resident:
         stepper.set_resident(True)
     stepped = False
+    nstep = 0
     while time < time_final:
         itime += 1
         time = time + dt
         stepper.ti_rk_bcl(q, qb, qp)
         stepped = True
+        nstep += 1
+        if flow_stats is not None and nstep % int(stats_every) == 0:
+            if resident and getattr(flow_stats, "needs_host_state", True):
+                stepper.sync(q, qb, qp)
+            flow_stats.add(q)
         if itime % irestart == 0 and dump_data:
             if resident:
                 stepper.sync(q, qb, qp)

@@ -69,6 +69,13 @@ def lib():
         L.hnumo_diag_geometry.argtypes = [vp, dp, C.c_int32, dp]
         L.hnumo_diagnostics.argtypes = [vp, C.c_int32, dp, C.c_int64]
         L.hnumo_layer_fields.argtypes = [vp, dp, C.c_int64]
+        L.hnumo_stats_begin.argtypes = [vp, C.c_int32, C.c_int32]
+        L.hnumo_stats_accumulate.argtypes = [vp]
+        L.hnumo_stats_sums.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64)]
+        L.hnumo_stats_set_sums.argtypes = [vp, dp, C.c_int64, C.c_int64]
+        L.hnumo_stats_fields.argtypes = [vp, dp, C.c_int64]
+        L.hnumo_stats_series.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]
+        L.hnumo_stats_end.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -271,6 +278,48 @@ class Engine:
         out = np.zeros((5, self.dims["npoin"], self.dims["nlayers"]), order="F")
         self._check(lib().hnumo_layer_fields(self.h, _dp(out), out.size))
         return out
+
+    # ---- online flow statistics on the device state (hnumo_stats_*; mirror: hnumo/flowstats.py)
+    def stats_begin(self, every: int = 0, series: int = 0):
+        """Allocate and zero the running sums (again: reset).  every = k >= 1: the engine samples
+        itself after every k-th successful step; series: samples the KE/VOL series can hold (0: none)."""
+        self._check(lib().hnumo_stats_begin(self.h, int(every), int(series)))
+
+    def stats_accumulate(self):
+        """One sample of the state on the device; nothing is copied back."""
+        self._check(lib().hnumo_stats_accumulate(self.h))
+
+    def stats_sums(self):
+        """(sums (4, npoin, nlayers) = S_h, S_uh, S_vh, S_e; the sample count)."""
+        out = np.zeros((4, self.dims["npoin"], self.dims["nlayers"]), order="F")
+        n = C.c_int64()
+        self._check(lib().hnumo_stats_sums(self.h, _dp(out), out.size, C.byref(n)))
+        return out, n.value
+
+    def stats_set_sums(self, sums, nsamples: int):
+        """Restore sums (4, npoin, nlayers) and a sample count, e.g. of a run being restarted."""
+        a = np.array(sums, dtype=np.float64, order="F")
+        size = 4 * self.dims["npoin"] * self.dims["nlayers"]
+        self._check(lib().hnumo_stats_set_sums(self.h, _dp(a, size, "sums"), a.size, int(nsamples)))
+
+    def stats_fields(self):
+        """(5, npoin, nlayers) = hbar, um, vm, mke, eke of the samples so far."""
+        out = np.zeros((5, self.dims["npoin"], self.dims["nlayers"]), order="F")
+        self._check(lib().hnumo_stats_fields(self.h, _dp(out), out.size))
+        return out
+
+    def stats_series(self, clear: bool = False):
+        """(2, nlayers, count) = (KE_k, VOL_k) per sample; clear empties the series afterwards."""
+        n = C.c_int64()
+        self._check(lib().hnumo_stats_series(self.h, None, 0, C.byref(n), 0))
+        out = np.zeros((2, self.dims["nlayers"], n.value), order="F")
+        if n.value or clear:
+            buf = out if out.size else np.zeros(1)
+            self._check(lib().hnumo_stats_series(self.h, _dp(buf), out.size, C.byref(n), int(clear)))
+        return out
+
+    def stats_end(self):
+        self._check(lib().hnumo_stats_end(self.h))
 
     def bench_steps(self, nsteps: int):
         t = C.c_double()

@@ -84,7 +84,8 @@ module hnumo_engine_c
         hnumo_set_resident, hnumo_sync, hnumo_last_error_c, hnumo_last_error, hnumo_get_field, &
         hnumo_set_summation, hnumo_get_summation, hnumo_stage_path, hnumo_persistent_info, hnumo_predict, &
         hnumo_rccl_unique_id, hnumo_persistent_stats, hnumo_diag_geometry, hnumo_diagnostics, &
-        hnumo_layer_fields
+        hnumo_layer_fields, hnumo_stats_begin, hnumo_stats_accumulate, hnumo_stats_sums, &
+        hnumo_stats_set_sums, hnumo_stats_fields, hnumo_stats_series, hnumo_stats_end
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
 
     interface
@@ -239,6 +240,61 @@ module hnumo_engine_c
             real(c_double), intent(out) :: out5(*)
             integer(c_int64_t), value :: n
         end function hnumo_layer_fields
+
+        ! Online flow statistics on the device state (see include/hnumo_engine.h): time means,
+        ! MKE / EKE and the KE series of the double-gyre post-processing, without hnumo_sync.
+        ! Begin before the time loop (every = k >= 1: the engine samples after every k-th successful
+        ! hnumo_ti_rk_bcl itself, so the loop does not change), fetch after it.
+        integer(c_int) function hnumo_stats_begin(eng, every, series_capacity) bind(C, name='hnumo_stats_begin')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: every, series_capacity
+        end function hnumo_stats_begin
+
+        integer(c_int) function hnumo_stats_accumulate(eng) bind(C, name='hnumo_stats_accumulate')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_stats_accumulate
+
+        ! out(4,npoin,nlayers) = S_h, S_uh, S_vh, S_e; n = 4*npoin*nlayers
+        integer(c_int) function hnumo_stats_sums(eng, out, n, nsamples) bind(C, name='hnumo_stats_sums')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: nsamples
+        end function hnumo_stats_sums
+
+        integer(c_int) function hnumo_stats_set_sums(eng, sums, n, nsamples) bind(C, name='hnumo_stats_set_sums')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: sums(*)
+            integer(c_int64_t), value :: n, nsamples
+        end function hnumo_stats_set_sums
+
+        ! out(5,npoin,nlayers) = hbar, um, vm, mke, eke; n = 5*npoin*nlayers
+        integer(c_int) function hnumo_stats_fields(eng, out, n) bind(C, name='hnumo_stats_fields')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_stats_fields
+
+        ! out(2,nlayers,count) = (KE_k, VOL_k) per sample; n = size(out) >= 2*nlayers*count;
+        ! clear = 1 empties the series after the copy
+        integer(c_int) function hnumo_stats_series(eng, out, n, count, clear) bind(C, name='hnumo_stats_series')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: count
+            integer(c_int32_t), value :: clear
+        end function hnumo_stats_series
+
+        integer(c_int) function hnumo_stats_end(eng) bind(C, name='hnumo_stats_end')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_stats_end
     end interface
 
 contains

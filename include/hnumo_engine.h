@@ -19,6 +19,10 @@
  *     hnumo_ti_barotropic_ssprk  -- ti_barotropic_ssprk_mlswe (mod_rk_mlswe.F90:19-151)
  *     hnumo_create_rhs_btp       -- create_rhs_btp            (mod_rhs_btp.F90:28-59)
  *
+ * Around the step, on the device state and without hnumo_sync: the run diagnostics
+ * (hnumo_diagnostics) and the online flow statistics -- time means, MKE / EKE, KE series
+ * (hnumo_stats_begin .. hnumo_stats_end).
+ *
  * Layout contract.  Every array is the reference's own Fortran (column-major) array,
  * 1-based integers where the reference is 1-based.  The reference's face arrays carry
  * a dead second face index (e.g. normal_vector(3,ngl,ngl,nface) of which only
@@ -250,6 +254,50 @@ int hnumo_sync(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime_df
 int hnumo_diag_geometry(hnumo_engine *eng, const double *coord, int32_t ldc, const double *wjac_df);
 int hnumo_diagnostics(hnumo_engine *eng, int32_t flags, double *out, int64_t n);
 int hnumo_layer_fields(hnumo_engine *eng, double *out5, int64_t n);
+
+/* Online flow statistics on the device state (additive in ABI v10): the time means, MKE / EKE and
+ * the kinetic-energy series that the double-gyre post-processing (Examples/double_gyre/
+ * compute_eke.m, compute_ke.m) forms from hundreds of snapshots, accumulated by HIP kernels where
+ * the state lives -- from every step if asked, no hnumo_sync.  Per owned node and layer, from
+ * q_df as diagnostics.F90:24-45 forms them: dp = q(1), h = (alpha_k/gravity)*dp, u = q(2)/dp,
+ * v = q(3)/dp, uh = u*h, vh = v*h, e = (0.5*(u*u + v*v))*h.  One SAMPLE adds h, uh, vh, e to the
+ * running sums S_h, S_uh, S_vh, S_e (plain adds in sample order, from +0.0) and, with a series,
+ * appends per layer KE_k = integral of e and VOL_k = integral of h over the rank's owned elements
+ * (per element the products jac_I * e_I added in node order; the element sums combined by a
+ * pairwise tree over the element positions: fixed bits, no floating-point atomics).  Every value
+ * has the bits of the numpy mirror hnumo/flowstats.py (HostFlowStats) on the synced states.
+ * Nodes of ghost elements are never accumulated and read 0 in every output.  DESIGN.md §6.1.1.
+ *
+ * hnumo_stats_begin: allocates and zeroes the sums; a second call resets them.  series_capacity:
+ *   samples the series can hold (0: no series, and no reduction work per sample).  every = 0: only
+ *   hnumo_stats_accumulate takes samples; every = k >= 1: the engine also takes one itself after
+ *   every k-th successful hnumo_ti_rk_bcl (hnumo_group_ti_rk_bcl for grouped engines) since begin,
+ *   once the step's abort / retry handling has finished; a step that returns non-zero is not
+ *   sampled.  If that sample finds the series full the step call returns 4 (the step is done).
+ * hnumo_stats_accumulate: one sample of the state on the device -- between the steps of a resident
+ *   engine or after the last call of a non-resident one; ordered after the step on the engine's
+ *   stream, outside the captured step, nothing copied back.  The step's launches, graph and bits
+ *   are the same with statistics on or off.
+ * hnumo_stats_sums / hnumo_stats_set_sums: out / in (4,npoin,nlayers) = S_h, S_uh, S_vh, S_e in the
+ *   index order of hnumo_layer_fields, n = 4*npoin*nlayers, and the sample count: a restarted run
+ *   restores them and goes on averaging.
+ * hnumo_stats_fields: out(5,npoin,nlayers), n = 5*npoin*nlayers, after nsamples samples:
+ *   hbar = S_h/nsamples, um = S_uh/S_h, vm = S_vh/S_h, mke = S_e/S_h, eke = mke - 0.5*(um*um + vm*vm).
+ * hnumo_stats_series: out(2,nlayers,count) = (KE_k, VOL_k) per sample; n = the doubles out can
+ *   hold, at least 2*nlayers*count; out = NULL (n = 0) only returns count.  clear = 1 empties the
+ *   series after the copy (the sums stay).  compute_ke.m's per-layer series is KE_k/VOL_k.
+ * hnumo_stats_end: frees the buffers; a no-op before hnumo_stats_begin.
+ * All return 4, with a message in hnumo_last_error, before hnumo_stats_begin, for a wrong n or
+ * negative arguments; a sample returns 4 before any state was uploaded and when the series is full
+ * (nothing is accumulated then); hnumo_stats_fields returns 4 with no samples.  Non-finite states
+ * are out of contract (the step returns 2 for them).                                          */
+int hnumo_stats_begin(hnumo_engine *eng, int32_t every, int32_t series_capacity);
+int hnumo_stats_accumulate(hnumo_engine *eng);
+int hnumo_stats_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples);
+int hnumo_stats_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples);
+int hnumo_stats_fields(hnumo_engine *eng, double *out, int64_t n);
+int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear);
+int hnumo_stats_end(hnumo_engine *eng);
 
 /* Summation order of the barotropic stage (no reference counterpart: the reference has
  * one order).  HNUMO_SUM_REFERENCE (the default) evaluates the volume integral and the
