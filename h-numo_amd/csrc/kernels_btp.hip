@@ -791,7 +791,34 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
             pa[n] = PSQ(n * NQ + iq);
             pb[n] = PSQ(n * NQ + jq);
           }
-          if (!I4 && g < 2) {
+          if (PERSIST && !I4 && g < 2) {
+            // (persistent: the same 25 terms in the same order with mm unrolled -- pb[mm] is a
+            // register, not a select chain over the array -- and row mm + 1's five 16-byte reads
+            // issued before row mm's arithmetic, so no row waits for its own reads)
+            const double2 *src = reinterpret_cast<const double2 *>(s_qb + 2 * g);  // node ip at [2 * ip]
+            double x0 = 0.0, x1 = 0.0;
+            double2 row[NGL], nxt[NGL];
+#pragma unroll
+            for (int n = 0; n < NGL; n++) row[n] = src[2 * n];
+#pragma unroll
+            for (int mm = 0; mm < NGL; mm++) {
+              if (mm + 1 < NGL) {
+#pragma unroll
+                for (int n = 0; n < NGL; n++) nxt[n] = src[2 * ((mm + 1) * NGL + n)];
+              }
+              asm volatile("" ::: "memory");
+#pragma unroll
+              for (int n = 0; n < NGL; n++) {
+                const double hi = pa[n] * pb[mm];  // PSIH(n,mm,iq,jq)
+                x0 = x0 + hi * row[n].x;
+                x1 = x1 + hi * row[n].y;
+              }
+#pragma unroll
+              for (int n = 0; n < NGL; n++) row[n] = nxt[n];
+            }
+            QI(2 * g, q) = x0;
+            QI(2 * g + 1, q) = x1;
+          } else if (!I4 && g < 2) {
             // broadcast LDS reads (every lane of the group reads the same node)
             double x0 = 0.0, x1 = 0.0;
 #pragma unroll 1
