@@ -199,6 +199,29 @@ def _brick_metrics(A, basis: Basis, mesh: BrickMesh):
 
 
 
+def derived_state(q_df, pbprime_df):
+    """The barotropic state qb_df(4,npoin) and the layer perturbations qprime_df(3,npoin,L) of a
+    layer state q_df(3,npoin,L) = (dp, u dp, v dp) over the reference pressure pbprime_df
+    (initial_conditions.F90:378-416): the statements of the initial conditions, for any q_df."""
+    npoin, L = q_df.shape[1], q_df.shape[2]
+    qprime_df = np.zeros((3, npoin, L), order="F")
+    ope = np.zeros(npoin)
+    for k in range(L):
+        ope = ope + q_df[0, :, k] / pbprime_df
+    for k in range(L):
+        qprime_df[0, :, k] = q_df[0, :, k] / ope
+    qb_df = np.zeros((4, npoin), order="F")
+    for k in range(L):
+        qb_df[0] = qb_df[0] + q_df[0, :, k]
+        qb_df[2] = qb_df[2] + q_df[1, :, k]
+        qb_df[3] = qb_df[3] + q_df[2, :, k]
+    qb_df[1] = qb_df[0] - pbprime_df
+    for k in range(L):
+        qprime_df[1, :, k] = q_df[1, :, k] / q_df[0, :, k] - qb_df[2] / qb_df[0]
+        qprime_df[2, :, k] = q_df[2, :, k] / q_df[0, :, k] - qb_df[3] / qb_df[0]
+    return qb_df, qprime_df
+
+
 def build_case(cfg: dict, dense: bool = True) -> Case:
     """Build mesh, tables and ICs.  ``dense`` adds the reference's dense tables (oracle only)."""
     nop, L = cfg["nop"], cfg["nlayers"]
@@ -331,23 +354,10 @@ def build_case(cfg: dict, dense: bool = True) -> Case:
 
     # layer state (initial_conditions.F90:378-416); one_plus_eta_temp starts at zero
     q_df = np.zeros((3, npoin, L), order="F")
-    qprime_df = np.zeros((3, npoin, L), order="F")
-    ope = np.zeros(npoin)
     for k in range(L):
         q_df[0, :, k] = (g / alpha[k]) * (z_int[:, k] - z_int[:, k + 1])
-        ope = ope + q_df[0, :, k] / pbprime_df
-    for k in range(L):
-        qprime_df[0, :, k] = q_df[0, :, k] / ope
     # u_df = v_df = 0 -> q_df(2:3) = 0
-    qb_df = np.zeros((4, npoin), order="F")
-    for k in range(L):
-        qb_df[0] = qb_df[0] + q_df[0, :, k]
-        qb_df[2] = qb_df[2] + q_df[1, :, k]
-        qb_df[3] = qb_df[3] + q_df[2, :, k]
-    qb_df[1] = qb_df[0] - pbprime_df
-    for k in range(L):
-        qprime_df[1, :, k] = q_df[1, :, k] / q_df[0, :, k] - qb_df[2] / qb_df[0]
-        qprime_df[2, :, k] = q_df[2, :, k] / q_df[0, :, k] - qb_df[3] / qb_df[0]
+    qb_df, qprime_df = derived_state(q_df, pbprime_df)
 
     # edge wave-speed coefficients (mod_initial_mlswe.F90:355-401)
     cm = np.sqrt(alpha[L - 1] * pbprime_face[1])

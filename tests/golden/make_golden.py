@@ -194,6 +194,66 @@ def make_geom(only=None):
         print(name, os.path.getsize(path))
 
 
+def make_matrix(only=None):
+    """The cells of tests/matrix.py, each from its own (rest or moving) state: the whole state after
+    the cell's steps (3x3 or 4x4 elements: as small as the unstrided fixtures above), the cell's
+    configuration and the parameters of tests/states.moving_state.  A cell with ad_mlswe > 0 stores
+    the predictor (mode "predict", as bump10s_predict above): the reference's own corrector reads
+    momenta it never assigns and its step is not finite there."""
+    import matrix as M
+    import states
+    for cell in M.CELLS:
+        if only and cell["name"] not in only:
+            continue
+        cfg, ov = M.cell_config(cell)
+        case = M.cell_case(cell)
+        mode, nsteps = ("predict", 1) if cell["shear"] else ("step", cell["nsteps"])
+        try:
+            out = O.run_reference(case, mode, nsteps)
+        except RuntimeError as e:
+            print(cell["name"], "NOT RUN BY THE REFERENCE HARNESS:", str(e)[-300:])
+            continue
+        keep = {"bundle_sha256": np.array(bundle_hash(case, mode, nsteps)), "stride": np.array(1),
+                "mode": np.array(mode), "nsteps": np.array(nsteps), "config": np.array(cfg),
+                "overrides": np.array(json.dumps(ov)), "state": np.array(cell["state"]),
+                "state_params": np.array(json.dumps(states.DEFAULT if cell["state"] == "moving" else {}))}
+        for k in ("q_df", "qb_df", "qprime_df"):
+            keep[k] = out[k]
+        path = os.path.join(HERE, "matrix_" + cell["name"] + ".npz")
+        np.savez_compressed(path, **keep)
+        print(cell["name"], os.path.getsize(path))
+
+
+def make_matrix_mpi(only=None):
+    """The processor-face halo from a moving state: the cells matrix.HALO_CELLS as 2-rank partitions
+    under mpiexec, every rank's whole state."""
+    import matrix as M
+    import states
+    from hnumo.facepart import face_partition
+    for name in M.HALO_CELLS:
+        if only and name not in only:
+            continue
+        cell = M.BY_NAME[name]
+        cfg, ov = M.cell_config(cell)
+        case = M.cell_case(cell)
+        # (3x3 elements do not split into two blocks: the Morton curve's 4 + 5 there)
+        order = "block" if ov["nelx"] % 2 == 0 else "morton"
+        parts = [face_partition(case, 2, r, order) for r in range(2)]
+        outs = O.run_reference_mpi(parts, "step", cell["nsteps"])
+        keep = {"config": np.array(cfg), "overrides": np.array(json.dumps(ov)), "nranks": np.array(2),
+                "order": np.array(order), "nsteps": np.array(cell["nsteps"]), "mode": np.array("step"),
+                "stride": np.array(1), "state": np.array(cell["state"]),
+                "state_params": np.array(json.dumps(states.DEFAULT))}
+        for r, (pc, o) in enumerate(zip(parts, outs)):
+            keep[f"bundle_sha256_r{r}"] = np.array(bundle_hash(pc, "step", cell["nsteps"]))
+            for k in ("q_df", "qb_df", "qprime_df"):
+                assert np.isfinite(o[k]).all(), (name, r, k)
+                keep[f"{k}_r{r}"] = o[k]
+        path = os.path.join(HERE, "matrix_mpi2_" + name + ".npz")
+        np.savez_compressed(path, **keep)
+        print(name, os.path.getsize(path))
+
+
 def overrides_of(g) -> dict:
     """Config overrides stored in a fixture (JSON; lists back to tuples)."""
     if "overrides" not in g:
@@ -240,6 +300,10 @@ if __name__ == "__main__":
         add_mpi_inputs_hash(args[1:])
     elif args and args[0] == "setup":
         make_setup(args[1:] or None)
+    elif args and args[0] == "matrix":
+        make_matrix(args[1:] or None)
+    elif args and args[0] == "matrix_mpi":
+        make_matrix_mpi(args[1:] or None)
     elif args and args[0] == "geom":
         make_geom(args[1:] or None)
     else:

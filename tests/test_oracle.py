@@ -134,6 +134,84 @@ def test_shear_predictor_golden(name, case_factory):
     assert np.array_equal(q, g["q_df"]) and np.array_equal(qb, g["qb_df"]) and np.array_equal(qp, g["qprime_df"])
 
 
+def _matrix_cells():
+    import matrix as M
+    return [c["name"] for c in M.CELLS]
+
+
+def _matrix_oracle(cell, case):
+    """(mode, nsteps, oracle state) of a matrix cell: its steps, or -- with ad_mlswe > 0, where the
+    reference's own corrector is not finite (test_shear_predictor_vs_reference_fortran) -- the
+    predictor."""
+    import oracle as O
+    mode, nsteps = ("predict", 1) if cell["shear"] else ("step", cell["nsteps"])
+    o = O.Oracle(case)
+    st = o.state()
+    if mode == "predict":
+        o.predict(*st)
+    else:
+        for _ in range(nsteps):
+            o.ti_rk_bcl(*st)
+    return mode, nsteps, st
+
+
+@pytest.mark.ref
+@pytest.mark.parametrize("name", _matrix_cells())
+def test_matrix_oracle_matches_reference_fortran(name, case_factory):
+    """Every cell of tests/matrix.py -- N = 2, 3, 4, 5, 7, one to three layers, every feature branch,
+    from states that move (tests/states.py) -- oracle vs the reference Fortran, bit for bit."""
+    import matrix as M
+    import oracle as O
+    cell = M.BY_NAME[name]
+    case = M.cell_case(cell, case_factory)
+    mode, nsteps, st = _matrix_oracle(cell, case)
+    ref = O.run_reference(case, mode, nsteps)
+    for k, a in zip(("q_df", "qb_df", "qprime_df"), st):
+        assert np.isfinite(ref[k]).all(), k
+        assert np.array_equal(a, ref[k]), k
+
+
+@pytest.mark.parametrize("name", _matrix_cells())
+def test_matrix_oracle_matches_golden(name, case_factory):
+    """The same on the committed fixtures (tests/golden/matrix_*.npz, make_golden.py matrix): the
+    state is rebuilt from the stored moving_state parameters and its bundle hash checked."""
+    import matrix as M
+    import states
+    import json
+    from util import overrides_of
+    cell = M.BY_NAME[name]
+    g = load("matrix_" + name)
+    case = case_factory(str(g["config"]), **overrides_of(g))
+    if str(g["state"]) == "moving":
+        case = states.moving_case(case, **json.loads(str(g["state_params"])))
+    mode, nsteps, st = _matrix_oracle(cell, case)
+    assert (mode, nsteps) == (str(g["mode"]), int(g["nsteps"]))
+    assert bundle_hash(case, mode, nsteps) == str(g["bundle_sha256"]), "setup inputs changed: regenerate golden"
+    for k, a in zip(("q_df", "qb_df", "qprime_df"), st):
+        assert np.isfinite(g[k]).all(), k
+        assert np.array_equal(a, g[k]), k
+
+
+def _halo_cells():
+    import matrix as M
+    return list(M.HALO_CELLS)
+
+
+@pytest.mark.parametrize("name", _halo_cells())
+def test_matrix_mpi_fixtures_are_current(name, case_factory):
+    """The 2-rank fixtures of the moving halo cells (read by tests/test_matrix_gpu.py) were made from
+    the inputs the partitioner builds today: every rank's bundle hash."""
+    import json
+    import states
+    from util import overrides_of
+    from hnumo.facepart import face_partition
+    g = load("matrix_mpi2_" + name)
+    case = states.moving_case(case_factory(str(g["config"]), **overrides_of(g)), **json.loads(str(g["state_params"])))
+    for r in range(int(g["nranks"])):
+        pc = face_partition(case, int(g["nranks"]), r, str(g["order"]))
+        assert bundle_hash(pc, "step", int(g["nsteps"])) == str(g[f"bundle_sha256_r{r}"]), r
+
+
 def test_shear_branch_is_live(case_factory):
     """ad_mlswe > 0 changes the predicted layer momenta (and only them)."""
     import oracle as O
