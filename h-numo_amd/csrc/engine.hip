@@ -84,7 +84,7 @@ struct hnumo_engine {
   // accumulators
   double *qacc, *facc, *nacc, *gfacc, *tau_wind_ave;
   // baroclinic scratch
-  double *slmf, *slmf_face, *dpp, *fmass, *fcons, *momL, *momR, *lapf, *rhs;
+  double *slmf, *slmf_face, *dpp, *fmass, *fcons, *momL, *lapf, *rhs;
   int *neg_flag, *h_neg;
   // graph
   hipGraph_t graph = nullptr;
@@ -95,9 +95,6 @@ struct hnumo_engine {
   hipEvent_t evk0 = nullptr, evk1 = nullptr;
   bool capturing = false, kernel_events = false, no_graph = false;
   int graph_env = -1;                        // HNUMO_GRAPH at create: 0 direct launches, 1 capture (RCCL too), -1 unset
-  bool no_fuse = false;                      // HNUMO_FUSE=0: face kernels and extract launches (A/B)
-  int sched_dbg = 0;                         // HNUMO_SCHED_DBG (timing experiments only, wrong results):
-                                             // 1 the interior launch skips its wait for the boundary one
   int summation = HNUMO_SUM_REFERENCE;        // hnumo_set_summation
   unsigned long long *stage_prof = nullptr;  // HNUMO_STAGE_PROF=1: per-element phase clocks
   int stage_dbg = 0;                         // HNUMO_STAGE_DBG: diagnostic phase switches (timing only)
@@ -168,7 +165,7 @@ struct hnumo_engine {
   double *lapq = nullptr;     // Laplacians [L][2][npoin] (barotropic: [2][npoin])
   int *fqLR = nullptr;        // [2][F][NQ] element-local quad point of each face quad point, left | right
   // bottom-layer qprime at the quad points, interpolated once per sub-cycle (StageArgs::qpq;
-  // botfr != 0; HNUMO_QPQ=0: every stage interpolates, for A/B timing)
+  // botfr != 0)
   double *qpq = nullptr;      // [E][3][Q]
   double *qsv = nullptr;      // [E][2][P][4] Shu-Osher states of the slim persistent sub-cycle (StageArgs::qsv)
   int *d_eperm = nullptr;     // persistent sub-cycle: workgroup -> element (SubArgs::eperm), NULL = identity
@@ -253,15 +250,12 @@ static void face_exchange_cdef(hnumo_engine *e);
 
 // ------------------------------------------------------------------ kernel dispatch
 // On a single rank every face's elements are in the element kernels' launches, so
-// fused_extract(e): the face traces qf of qprime are written by the kernels that write qprime
+// (fused_extract) the face traces qf of qprime are written by the kernels that write qprime
 // (mom_elem, cons_elem) instead of by extract launches after them (the face traces of a qprime
-// uploaded by the host are extracted at the upload, upload_state);
-// fused_faces(e): the layer mass and consistency fluxes of a face are formed by the element
-// kernels of both its elements instead of by the face kernels before them (HNUMO_FUSE=0: off).
-static bool fused_extract(const hnumo_engine *e) {
-  return e->comm_mode == 0 && e->nranks == 1 && !e->face_halo && !e->no_fuse;
-}
-static bool fused_faces(const hnumo_engine *e) { return fused_extract(e); }
+// uploaded by the host are extracted at the upload, upload_state), and the layer mass and
+// consistency fluxes of a face are formed by the element kernels of both its elements instead of
+// by the face kernels before them.  Multi-rank engines run the extract launches and face kernels.
+static bool fused_extract(const hnumo_engine *e) { return e->comm_mode == 0 && e->nranks == 1 && !e->face_halo; }
 
 template <int NGL, int NQ>
 struct Launch {
@@ -340,9 +334,6 @@ struct Launch {
     e->occ_ncu = ncu;
     const bool est = e->persist_guard & 1;
     e->persistent_ok[0] = !est || (long)nb0 * ncu >= e->nelem_owned;
-    // the slim arena keeps the bottom-layer qprime only for the first stage: the later ones need
-    // the per-sub-cycle quad-point scratch
-    if (StageCfg<NGL, NQ, false>::SLIM && e->m.botfr && !e->qpq) e->persistent_ok[0] = false;
     e->persistent_ok[1] = !est || (long)nb1 * ncu >= e->nelem_owned;
     e->regacc[0] = StageCfg<NGL, NQ, false>::REGACC;
     e->regacc[1] = StageCfg<NGL, NQ, true>::REGACC;
@@ -352,10 +343,9 @@ struct Launch {
     launch_sub(e, sum, SubArgs{e->d_stages[0], 0, e->epoch, e->sub_done, e->sub_arrive, e->neg_flag, nullptr, e->d_eperm});
   }
   // face traces of elements [e0, e0+n) into their neighbours' slots
-  static void grad_trace(hnumo_engine *e, const double *qb, double *gt, int e0, int n, TraceGranule *gtr = nullptr) {
+  static void grad_trace(hnumo_engine *e, const double *qb, double *gt, int e0, int n) {
     if (n > 0) {
-      hipLaunchKernelGGL((grad_trace_kernel<NGL, NQ>), dim3(n), dim3(64), 0, e->stream, e->m, qb, gt, e0, gtr,
-                         e->epoch);
+      hipLaunchKernelGGL((grad_trace_kernel<NGL, NQ>), dim3(n), dim3(64), 0, e->stream, e->m, qb, gt, e0);
       kmark(e, "grad_trace");
     }
   }
@@ -370,11 +360,11 @@ struct Launch {
   }
   // (qp_avg, qf_avg: the corrector's averages qp = 0.5*(qp + qp_avg), qf = 0.5*(qf_avg + qf) formed
   // and written back by the two kernels, ti_rk_bcl.F90:64-65)
-  // (single rank, fused_faces: the element kernel forms the face part as well; the corrector's
+  // (single rank, fused_extract: the element kernel forms the face part as well; the corrector's
   // averaged face traces then go to qf_out = e->qfa, which the rest of the corrector reads)
   static void bcl_coeffs(hnumo_engine *e, double *qp, double *qf, const double *qp_avg = nullptr,
                          const double *qf_avg = nullptr, double *qf_out = nullptr) {
-    const bool fz = fused_faces(e);
+    const bool fz = fused_extract(e);
     hipLaunchKernelGGL((bcl_coeffs_elem_kernel<NGL, NQ>), dim3(e->nelem), dim3(Blk<NGL, NQ>::BSW), 0, e->stream, e->m, qp,
                        qp_avg, e->qcoef, e->ncoef, e->dpp_graduv, e->dpprime_visc, e->ecoef, fz ? qf : nullptr,
                        qf_avg, qf_out, e->fcoef, e->fncoef, e->gdpp_face, e->efcoef);
@@ -415,9 +405,9 @@ struct Launch {
   }
   // layer mass update (owned elements); produces dp' (e->dpp) for the consistency step
   // (q_in: the layer thicknesses entering the update; q: where they are written)
-  // (single rank: the element kernels form their faces' fluxes themselves, fused_faces)
+  // (single rank: the element kernels form their faces' fluxes themselves, fused_extract)
   static void mass(hnumo_engine *e, const double *qp, const double *qf, const double *q_in, double *q) {
-    const bool fz = fused_faces(e);
+    const bool fz = fused_extract(e);
     if (!fz)
       hipLaunchKernelGGL((mass_flux_face_kernel<NGL, NQ>), dim3(e->nface), dim3(64), 0, e->stream, e->m, qf, e->facc,
                          e->fmass, e->slmf_face);
@@ -429,7 +419,7 @@ struct Launch {
   }
   // (qf: the face traces of qp_out's thickness written by cons_elem itself -- fused extract)
   static void cons(hnumo_engine *e, double *q, double *qp_out, int finalize_dp, double *qf = nullptr) {
-    const bool fz = fused_faces(e);
+    const bool fz = fused_extract(e);
     if (!fz)
       hipLaunchKernelGGL((cons_flux_face_kernel<NGL, NQ>), dim3(e->nface), dim3(64), 0, e->stream, e->m, e->dpp,
                          e->facc, e->slmf_face, e->fcons, e->face_halo ? e->cdef : nullptr);
@@ -453,10 +443,10 @@ struct Launch {
                        const double *qf_avg0 = nullptr, double *qf_out = nullptr) {
     if (e->lapq_on) lapq_bcl(e, qp_in);
     hipLaunchKernelGGL((mom_flux_face_kernel<NGL, NQ>), dim3(e->nface), dim3(64), 0, e->stream, e->m, qf, e->facc,
-                       e->gdpp_face, e->gfacc, e->momL, e->momR, e->lapf, qf_avg0);
+                       e->gdpp_face, e->gfacc, e->momL, e->lapf, qf_avg0);
     kmark(e, "mom_flux_face");
     hipLaunchKernelGGL((mom_elem_kernel<NGL, NQ>), dim3(e->nelem_owned), dim3(MomCfg<NGL, NQ>::BS), 0, e->stream, e->m, qp_in, e->qacc,
-                       e->nacc, e->dpp_graduv, e->dpprime_visc, e->momL, e->momR, e->lapf, qb, q_in, q, qp_out, mode,
+                       e->nacc, e->dpp_graduv, e->dpprime_visc, e->momL, e->lapf, qb, q_in, q, qp_out, mode,
                        e->lapq_on ? e->lapq : nullptr, e->dpp2, e->neg_flag, qp_avg0, qf_out);
     kmark(e, "mom_elem");
   }
@@ -778,29 +768,27 @@ static void launch_copy(hnumo_engine *e, double *dst, const double *src, size_t 
   (void)hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, e->stream);
 }
 
-// Sub-cycle prologue (mod_rk_mlswe.F90:45-72): zero the time averages, copy the state into
-// stage buffer 0 and bump the persistent kernel's epoch -- one launch instead of four memsets,
-// a copy and a one-thread kernel (each a graph node of ~4 us at this size).
+// Sub-cycle prologue (mod_rk_mlswe.F90:45-72): zero the time averages and copy the state into
+// stage buffer 0 -- one launch instead of four memsets and a copy (each a graph node of ~4 us at
+// this size).
 __global__ void subcycle_prologue_kernel(double *qacc, size_t nqa, double *facc, size_t nfa, double *nacc, size_t nna,
-                                         double *gfacc, size_t nga, double *qbuf0, const double *qb, size_t nqb,
-                                         unsigned long long *epoch) {
+                                         double *gfacc, size_t nga, double *qbuf0, const double *qb, size_t nqb) {
   const size_t s = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (size_t i = t0; i < nqa; i += s) qacc[i] = 0.0;
   for (size_t i = t0; i < nfa; i += s) facc[i] = 0.0;
   for (size_t i = t0; i < nna; i += s) nacc[i] = 0.0;
   for (size_t i = t0; i < nga; i += s) gfacc[i] = 0.0;
   for (size_t i = t0; i < nqb; i += s) qbuf0[i] = qb[i];
-  if (epoch && t0 == 0) *epoch = *epoch + 1;
 }
 
 // (zero_acc false: the persistent kernel writes every average itself, StageCfg::REGACC)
-static void subcycle_prologue(hnumo_engine *e, const double *qb_state, unsigned long long *epoch, bool zero_acc) {
+static void subcycle_prologue(hnumo_engine *e, const double *qb_state, bool zero_acc) {
   const size_t z = zero_acc ? 1 : 0;
   const size_t nqa = z * QA_N * (size_t)e->npq, nfa = z * FA_N * 4 * (size_t)e->nelem * e->nq;
   const int blocks = (int)std::min<size_t>((std::max<size_t>(nqa, 4 * (size_t)e->npoin) + 255) / 256, 2048);
   hipLaunchKernelGGL(subcycle_prologue_kernel, dim3(blocks), dim3(256), 0, e->stream, e->qacc, nqa, e->facc, nfa,
                      e->nacc, z * NA_N * (size_t)e->npoin, e->gfacc, z * 8 * 4 * (size_t)e->nelem * e->ngl,
-                     e->qbuf[0], qb_state, 4 * (size_t)e->npoin, epoch);
+                     e->qbuf[0], qb_state, 4 * (size_t)e->npoin);
   kmark(e, "subcycle_prologue");
 }
 
@@ -891,7 +879,7 @@ static void launch_subcycle(hnumo_engine *e, double *dst, const double *qp, bool
   // persistent with register averages: the kernel writes them, zeroed and scaled as below
   const bool racc = pers && e->regacc[e->summation] && !(e->stage_dbg & 32);
   // (the first stage stores the time averages unless method_visc == 1: no zeroing, StageArgs::accumulate)
-  if (!racc) subcycle_prologue(e, e->qb, nullptr, e->lapq_on || e->acc_zero);
+  if (!racc) subcycle_prologue(e, e->qb, e->lapq_on || e->acc_zero);
   if (!pers) exchange_qb(e, e->qbuf[0]);
   if (!pers) DISPATCH(e, grad_trace(e, e->qbuf[0], e->gtrace[0], 0, e->nelem));  // (persistent: its stage 0)
   const int K = e->K, NB = e->p.N_btp;
@@ -915,10 +903,10 @@ static void launch_subcycle(hnumo_engine *e, double *dst, const double *qp, bool
     cur = stage_table(e, qp, st);
     if (timed && e->kernel_events) (void)hipEventRecord(e->evk0, e->stream);
     // (stop events: each launch signals its own completion, no record packet between the
-    // interior launches; HNUMO_SCHED_DBG 2, diagnostics builds, restores the recorded events for A/B)
+    // interior launches; a captured step records events instead)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(e->stream, &cap);
-    const bool sev = !(e->sched_dbg & 2) && e->ev_Bs[0] && cap == hipStreamCaptureStatusNone;
+    const bool sev = e->ev_Bs[0] && cap == hipStreamCaptureStatusNone;
     // ev_fork orders stream2 after the sub-cycle input's traces (grad_trace, trace_exchange above):
     // that is B_0's whole dependency, so B_0 waits for nothing else
     (void)hipEventRecord(e->ev_fork, e->stream);
@@ -930,7 +918,7 @@ static void launch_subcycle(hnumo_engine *e, double *dst, const double *qp, bool
       a.elist = e->d_elB;
       DISPATCH(e, stage(e, a, e->nB, e->stream2, sev ? e->ev_Bs[i & 1] : nullptr));
       if (!sev) (void)hipEventRecord(e->ev_B[i & 1], e->stream2);
-      if (i > 0 && !(e->sched_dbg & 1))
+      if (i > 0)
         (void)hipStreamWaitEvent(e->stream, sev ? e->ev_Bs[(i - 1) & 1] : e->ev_B[(i - 1) & 1], 0);
       const StageArgs aB = a;
       a.elist = e->d_elI;
@@ -1001,7 +989,7 @@ static void launch_step(hnumo_engine *e) {
   launch_predict(e);
   if (!fx) DISPATCH(e, extract(e, e->qp2, e->qf2, 0));
   // correction (ti_rk_bcl.F90:62-85); qfc = the averaged qprime_face2 (fused faces: e->qfa)
-  double *qfc = fused_faces(e) ? e->qfa : e->qf2;
+  double *qfc = fused_extract(e) ? e->qfa : e->qf2;
   DISPATCH(e, bcl_coeffs(e, e->qp2, e->qf2, e->qp, e->qf, qfc == e->qf2 ? nullptr : qfc));
   launch_subcycle(e, e->qb, e->qp2, true);
   DISPATCH(e, mass(e, e->qp2, qfc, e->q, e->q));
@@ -1079,7 +1067,7 @@ static int open_device(hnumo_engine *eng, int *ncu) {
 
 // what the environment asks for beyond the engine's own fields
 struct Knobs {
-  bool qpq = false, stage_prof = false;  // buffers to allocate
+  bool botfr = false, stage_prof = false;  // buffers to allocate (botfr: hnumo_engine::qpq)
   bool persist_on = true, place = false, glue_perm = false;
 };
 
@@ -1096,10 +1084,6 @@ static int read_knobs(hnumo_engine *eng, int ncu, Knobs &k) {
   }
   if (HNUMO_DIAG)  // (diagnostics builds only; see engine_internal.h)
     if (const char *sd = env_knob(eng, "HNUMO_STAGE_DBG")) eng->stage_dbg = atoi(sd);
-  if (const char *fz = env_knob(eng, "HNUMO_FUSE")) eng->no_fuse = fz[0] == '0';
-  // (bit 1 drops a required stream dependency -- wrong results, timing only: diagnostics builds)
-  if (HNUMO_DIAG)
-    if (const char *sd = env_knob(eng, "HNUMO_SCHED_DBG")) eng->sched_dbg = atoi(sd);
   // per-stage kernel arena: on meshes that take several residency rounds per stage, the arena
   // sized for 4 workgroups per CU (1-row term chunks) -- 1.566 -> 1.517 ms per stage at C4
   // (tools/ab_env.py, round 2); small meshes keep the 3-per-CU arena
@@ -1110,10 +1094,7 @@ static int read_knobs(hnumo_engine *eng, int ncu, Knobs &k) {
   eng->bcl_big = eng->nelem_owned >= 2048;
   if (const char *bb = env_knob(eng, "HNUMO_BCL_BIG")) eng->bcl_big = bb[0] == '1';
   if (const char *az = env_knob(eng, "HNUMO_ACC_ZERO")) eng->acc_zero = az[0] == '1';
-  {
-    const char *qv = env_knob(eng, "HNUMO_QPQ");
-    k.qpq = eng->p.botfr && !(qv && atoi(qv) == 0);
-  }
+  k.botfr = eng->p.botfr != 0;
   if (const char *sp = HNUMO_DIAG ? env_knob(eng, "HNUMO_STAGE_PROF") : nullptr) k.stage_prof = sp[0] == '1';
   const char *pe = env_knob(eng, "HNUMO_PERSISTENT", false);
   k.persist_on = !(pe && pe[0] == '0');
@@ -1175,7 +1156,6 @@ static int create_buffers(hnumo_engine *eng, const SetupPlan &pl, const hnumo_st
   eng->dpp = dalloc<double>(eng, npoin * L);
   eng->fmass = dalloc<double>(eng, FQ * L); eng->fcons = dalloc<double>(eng, FQ * L);
   eng->momL = dalloc<double>(eng, 4 * (size_t)E * 2 * nq * L);  // [slot][L][2][NQ] (MSLOT)
-  eng->momR = nullptr;
   eng->lapf = dalloc<double>(eng, 4 * (size_t)E * 2 * ngl * L);  // [slot][L][2][NGL]
   if (eng->lapq_on) {  // quad-point LDG (kernels_lapq.hip)
     eng->dpq = dalloc<double>(eng, npq * L);
@@ -1185,7 +1165,7 @@ static int create_buffers(hnumo_engine *eng, const SetupPlan &pl, const hnumo_st
   }
   eng->rhs = dalloc<double>(eng, 3 * npoin);
   eng->neg_flag = dalloc<int>(eng, 1);
-  if (k.qpq) eng->qpq = dalloc<double>(eng, (size_t)E * 3 * nq * nq);
+  if (k.botfr) eng->qpq = dalloc<double>(eng, (size_t)E * 3 * nq * nq);
   if (k.stage_prof) eng->stage_prof = dalloc<unsigned long long>(eng, (size_t)E * 32);
   eng->steps_done = dalloc<unsigned>(eng, 1);
   if (eng->alloc_failed) return fail(eng, HNUMO_ERR_DEVICE, "hipMalloc failed (out of device memory?)");
@@ -2126,7 +2106,7 @@ int hnumo_create_rhs_btp(hnumo_engine *eng, double *rhs, const double *qb_df, co
   HIPCHK(hipSetDevice(eng->device));
   rc = upload_state(eng, nullptr, qb_df, qprime_df);
   if (rc) return rc;
-  subcycle_prologue(eng, eng->qb, nullptr, true);  // zeroed time averages (qbuf[0] is the rhs-only output slot)
+  subcycle_prologue(eng, eng->qb, true);  // zeroed time averages (qbuf[0] is the rhs-only output slot)
   DISPATCH(eng, grad_trace(eng, eng->qb, eng->gtrace[0], 0, eng->nelem));
   trace_exchange(eng, eng->gtrace[0], eng->stream);
   StageArgs a{};

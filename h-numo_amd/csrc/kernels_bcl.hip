@@ -126,16 +126,12 @@ struct BasisGather {
 #define HE_DF(n, m, i, j) (s_dpsi[(n)*NGL + (i)] * s_psi[(m)*NGL + (j)])
 #define HN_DF(n, m, i, j) (s_psi[(n)*NGL + (i)] * s_dpsi[(m)*NGL + (j)])
 
-// Workgroup barrier for LDS hand-offs only (no release fence: outstanding global stores of the
-// wave are not drained, unlike __syncthreads())
-// mom_elem phase 2: the interface-height gradient sums on their own threads first (see GZS there)
-#ifndef HNUMO_MOM_GZS
-#define HNUMO_MOM_GZS 1
-#endif
 // the element of this block (DevMesh::eperm)
 __device__ __forceinline__ int blk_elem(const DevMesh &m) {
   return m.eperm ? __builtin_amdgcn_readfirstlane(m.eperm[blockIdx.x]) : (int)blockIdx.x;
 }
+// Workgroup barrier for LDS hand-offs only (no release fence: outstanding global stores of the
+// wave are not drained, unlike __syncthreads())
 #define BCL_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // Term buffers of ordered_node_sums: chunks of RC quad rows (RC | NQ) for NT chains, two buffers
@@ -1423,11 +1419,11 @@ __global__ void __launch_bounds__((Blk<NGL, NQ>::BSW))
 // element-side slot (fslotL / fslotR) of that side, momL[slot][L][2][NQ] (MSLOT; the element
 // kernel applies -/+ (wq*hi)*value in reference order and loads its four slots without first
 // reading its face ids), and per face node wq*psi(n,n)*flux (LDG; + for left, - for right) into
-// both sides' slots, lap[slot][L][2][NGL].  (momR is unused.)
+// both sides' slots, lap[slot][L][2][NGL].
 template <int NGL, int NQ>
 __global__ void __launch_bounds__(64)
     mom_flux_face_kernel(DevMesh m, const double *qf, const double *facc, const double *gdpp_face,
-                         const double *gfacc, double *momL, double *momR, double *lap, const double *qf_avg0) {
+                         const double *gfacc, double *momL, double *lap, const double *qf_avg0) {
   // qf_avg0 (the corrector): the face thickness traces enter as 0.5*(qf_avg0 + qf) (component 1,
   // ti_rk_bcl.F90:80), formed on load
   const int f = blockIdx.x, tid = threadIdx.x, F = m.nface, L = m.L;
@@ -1737,9 +1733,9 @@ struct MomCfg {
 template <int NGL, int NQ>
 __global__ void __launch_bounds__(256, (MomCfg<NGL, NQ>::MINW))
     mom_elem_kernel(DevMesh m, const double *qp_in, const double *qacc, const double *nacc, const double *dpp_graduv,
-                    const double *dpprime_visc, const double *momL, const double *momR, const double *lapf,
-                    const double *qb, const double *q_in, double *q, double *qp_out, int mode, const double *lapx,
-                    const double *dpp2, int *flag, const double *qp_avg0, double *qf) {
+                    const double *dpprime_visc, const double *momL, const double *lapf, const double *qb,
+                    const double *q_in, double *q, double *qp_out, int mode, const double *lapx, const double *dpp2,
+                    int *flag, const double *qp_avg0, double *qf) {
   // qf (single rank): extract_qprime_df_face of the new qprime fused into the tail
   // (extract_node_faces), in place of the extract launch after this kernel
   // qp_avg0 (the corrector, non-NULL: dpp2 is then not read): the layer thicknesses qprime(1)
@@ -1960,7 +1956,7 @@ __global__ void __launch_bounds__(256, (MomCfg<NGL, NQ>::MINW))
   // GZS: the interface-height gradients gz0[k] (x), gz1[k] (y) at the quad points (the coupling's
   // 25-term sums, :339-349) first, one thread per (quad point, direction), into s_gz (in the part
   // of s_ivtb past the interpolations, free until phase 3); the coupling then reads them
-  constexpr bool GZS = HNUMO_MOM_GZS && 2 * Q <= BS && MAXL * 5 * Q + 2 * (MAXL + 1) * Q <= IVTB;
+  constexpr bool GZS = 2 * Q <= BS && MAXL * 5 * Q + 2 * (MAXL + 1) * Q <= IVTB;
   double(*s_gz)[MAXL + 1][Q] = reinterpret_cast<double(*)[MAXL + 1][Q]>(s_ivtb + MAXL * 5 * Q);
   if constexpr (GZS) {
     if (tid < 2 * Q) {

@@ -51,7 +51,6 @@ constexpr int PRIO_B = 1, PRIO_S = 2, PRIO_E = 3;
 // 2048 E2 trace stores, 4096 the A copies of the records (tools/dbg_sweep.py, tools/pmc_ablate.sh)
 // -- and StageArgs::prof, the per-element phase clocks (tools/stage_profile.py)
 #define DBG(bit) (HNUMO_DIAG && (a.dbg & (bit)))
-#define DBGX(bit) DBG(bit)
 #define PROF (HNUMO_DIAG && a.prof)
 #define SETPRIO_IF(cond, hi, lo)        \
   do {                                  \
@@ -204,25 +203,29 @@ struct StageCfg {
   static constexpr int ECO = eco_stride(Q, P);              // ecoef record per element (4Q + 5P, even)
   static constexpr int NB = 2 * NGL * NQ + NGL * NGL;       // psiq, dpsiq, dpsi (+ a zero slot)
   static_assert(Q <= BS, "one quad-point task per thread");
-  static constexpr bool OTF = !SF && NGL >= OTF_MIN_NGL;
-  // SLIM, SLATE, OPAIR and QPM name four aspects of the one OTF arena (all on together with OTF):
-  // SLIM (OTF): an arena small enough for 3 workgroups per CU, so the persistent sub-cycle holds
+  // SLIM: the one arena of the on-the-fly volume integral (OTF_MIN_NGL), in four aspects.
+  // An arena small enough for 3 workgroups per CU, so the persistent sub-cycle holds
   // all 625 elements of dg25 at N=7 at once.  The last wave (EW), idle beside the on-the-fly
   // volume sums of waves 0..2, runs the LDG volume fluxes, LDG face fluxes and the Laplacian
   // there and then E1; what only E1 and qq read -- the Shu-Osher states qb0/qb2, massinv,
   // pbprime, the nodal coefficients, the Laplacian -- lives in that wave's registers (loaded
   // from global memory while waves 0..2 sum) instead of LDS; the new state overwrites the
   // stage input in place; the bottom-layer qprime (A2 only) overlays the nodal gradients.
-  static constexpr bool SLIM = OTF;
-  // SLATE (SLIM): the face fluxes also run on the last wave in D, so the neighbour traces are
+  //
+  // The face fluxes also run on the last wave in D, so the neighbour traces are
   // needed (persistent: polled) only there, behind the element's own interpolation, quad-point
   // physics and most of its volume sums -- the neighbours' stage-to-stage skew hides behind them;
-  // the volume sums' face lifts follow a barrier
-  static constexpr bool SLATE = SLIM;
-  // OPAIR (SLATE): a node's component-1 and -2 volume sums on one thread (see otf_sum12) in the
+  // the volume sums' face lifts follow a barrier.
+  //
+  // A node's component-1 and -2 volume sums run on one thread (see otf_sum12) in the
   // per-stage kernel (dg25N7L3: 65.0 -> 57.0 us per launch); the persistent sub-cycle instead sums
-  // all three components of a node on one thread (otf_sum012, TRIPLE)
-  static constexpr bool OPAIR = SLATE;
+  // all three components of a node on one thread (otf_sum012, TRIPLE).
+  //
+  // The quad-point values lie by quad point, s_qv [4][Q][2] = pairs of (w, the 7 integrand factors) --
+  // A2's interpolations in slots 0..3 and the bottom layer's in 4..6 until B overwrites them -- so the
+  // on-the-fly sums read a quad point's 8 values as four ds_read_b128 from one address; w moves out of
+  // s_qk, which keeps the metric pairs alone (16-byte aligned).
+  static constexpr bool SLIM = !SF && NGL >= OTF_MIN_NGL;
   static constexpr int EW = BS / 64 - 1;
   // LEAN (the per-stage kernel's arenas for large meshes, NBK != 0): less fixed LDS so that more
   // workgroups fit a CU or more quad rows fit a term chunk -- E1 on the last wave (the volume-sum
@@ -230,7 +233,7 @@ struct StageCfg {
   // during D) instead of LDS; the right-hand side and the Laplacian in the term buffer that is dead
   // in the last D phase, the new state in the other one (dead after D), the face-quad traces of
   // FPRE in term buffer 0 (A2 -> B; D0 writes it first)
-  static constexpr bool LEAN = NBK != 0 && !SF && !OTF;
+  static constexpr bool LEAN = NBK != 0 && !SF && !SLIM;
   // G16: 16-byte LDS-DMA for the element's records (glds_copy).  Not in the slim N=7 arena: there
   // it measured slower (dg25N7L3 persistent 50.2 -> 53.0 us per stage, while dg25L3 persistent
   // 13.0 -> 12.7 and C4 1.322 -> 1.296 ms; profiles/r03h)
@@ -241,31 +244,24 @@ struct StageCfg {
   // (the regions LDS-DMA writes start on 16 bytes: ev; not the slim arena, which keeps the dword
   // copies -- see G16)
   static constexpr int ev(int x) { return SLIM ? x : (x + 1) & ~1; }
-  // QPM (SLIM): the quad-point values by quad point, s_qv [4][Q][2] = pairs of (w, the 7 integrand factors) --
-  // A2's interpolations in slots 0..3 and the bottom layer's in 4..6 until B overwrites them -- so the
-  // on-the-fly sums read a quad point's 8 values as four ds_read_b128 from one address; w moves out of
-  // s_qk, which keeps the metric pairs alone (16-byte aligned)
-  static constexpr bool QPM = SLIM;
-  static constexpr int QKR = QPM ? 4 : QE_KEEP;  // s_qk rows
+  static constexpr int QKR = SLIM ? 4 : QE_KEEP;  // s_qk rows (SLIM: the metric pairs alone)
   static constexpr int al2(int x) { return (x + 1) & ~1; }
   static constexpr int O_BASIS = 0, O_EREC = ev(O_BASIS + NB + 1), O_QB = ev(O_EREC + ERSD), O_Q0 = O_QB + 4 * P,
                        O_Q2 = O_Q0 + ((SLIM || LEAN) ? 0 : 4 * P),
-                       O_QK = QPM ? al2(O_Q2) : O_Q2 + ((SLIM || LEAN) ? 0 : 4 * P),
+                       O_QK = SLIM ? al2(O_Q2) : O_Q2 + ((SLIM || LEAN) ? 0 : 4 * P),
                        O_NS = ev(O_QK + QKR * Q),
                        O_NC = ev(O_NS + (SLIM ? NE_LDS : NE_N) * P), O_UV = O_NC + (SLIM ? 0 : 5 * P), O_WN = O_UV + 2 * P;
   // working arrays: quad-point values (exact: the 7 integrand factors; SF: the 8 weighted
   // integrands F1,F2,G0..G2,H0..H2), B outputs, then a region written only after B that the
   // SF variant also uses for the interpolation partials Y [NYV][NGL][NQ] (A2 -> B)
-  static constexpr int NQV = (SF || QPM) ? 8 : 7, NYV = 7;
+  static constexpr int NQV = (SF || SLIM) ? 8 : 7, NYV = 7;
   // (SLIM: no Laplacian / new-state buffers; the face-quad traces of FPRE, A2 -> B, share the W
   // region with qq and rhs, D -> E.  O_QN: the per-stage kernel's new state; the persistent
   // sub-cycle updates s_qb in place and knows these words only as the tail of FPRE's traces)
-  static constexpr int O_QV = QPM ? al2(O_WN + 8 * NGL) : O_WN + 8 * NGL, O_GR = ev(O_QV + NQV * Q), O_FQ = O_GR + 4 * P, O_FL = O_FQ + 16 * NQ,
+  static constexpr int O_QV = SLIM ? al2(O_WN + 8 * NGL) : O_WN + 8 * NGL, O_GR = ev(O_QV + NQV * Q), O_FQ = O_GR + 4 * P, O_FL = O_FQ + 16 * NQ,
                        O_W = O_FL + 8 * NGL, O_QQ = O_W, O_RHS = O_QQ + 4 * P, O_LAP = O_RHS + (LEAN ? 0 : 3 * P),
                        O_QN = O_LAP + ((SLIM || LEAN) ? 0 : 2 * P), O_Y = O_W,
-                       W_END0 = O_QN + ((SLIM || LEAN) ? 0 : 4 * P),
-                       QN_END_W = W_END0 - O_W,
-                       W_END = W_END0,
+                       W_END = O_QN + ((SLIM || LEAN) ? 0 : 4 * P),
                        O_BIN = ev((SF && O_Y + NYV * NGL * NQ > W_END) ? O_Y + NYV * NGL * NQ : W_END);
   // B inputs: the bottom-layer qprime, face statics, neighbour traces, face coefficients,
   // reloaded every stage (the persistent kernel: re-fetched behind E1) and overlaid by term
@@ -284,24 +280,25 @@ struct StageCfg {
   static constexpr int RC0 = rc_fit(TAV);
   static constexpr int RCM = RC0 < 1 ? 1 : (RC0 > NQ ? NQ : RC0);
   static constexpr int NCH = (NQ + RCM - 1) / RCM, RC = (NQ + NCH - 1) / NCH, QC = RC * NQ;
-  static constexpr int QCP = QC | 1, TSZ = OTF ? 0 : 3 * P * QCP;
-  static constexpr int TB0 = ev(TSZ > B_SIZE ? TSZ : B_SIZE), TB1 = 0;
+  static constexpr int QCP = QC | 1, TSZ = SLIM ? 0 : 3 * P * QCP;
+  // (term buffer 1 starts the region, over the B inputs; buffer 0 lies behind both, at TB0)
+  static constexpr int TB0 = ev(TSZ > B_SIZE ? TSZ : B_SIZE);
   // SF: first-pass contraction partials U, W [3][2][NGL][NQ] (C1 runs the LDG face fluxes)
   static constexpr int UWSZ = 3 * 2 * NGL * NQ, B_UW = B_SIZE;
   static constexpr int ARENA = O_B + (SF ? B_UW + UWSZ : TB0 + TSZ);
-  static constexpr int NGR = (32 * NGL + 63) / 64;  // granules per lane of the polling wave (SLATE)
-  // B task ranges: quad points [0,Q) | face points [OF,OF+4NQ) (not SLATE) | nodal grad
+  static constexpr int NGR = (32 * NGL + 63) / 64;  // granules per lane of the polling wave (SLIM)
+  // B task ranges: quad points [0,Q) | face points [OF,OF+4NQ) (not SLIM) | nodal grad
   // [OG,OG+P) | LDG face nodes [OL,OL+4NGL) (SF: C1), on their own
   // waves when they fit
   static constexpr int RU = 64, OFa = ((Q + RU - 1) / RU) * RU,
-                       OGa = SLATE ? OFa : ((OFa + 4 * NQ + RU - 1) / RU) * RU;
+                       OGa = SLIM ? OFa : ((OFa + 4 * NQ + RU - 1) / RU) * RU;
   static constexpr bool WIDE = OGa + P + (SF ? 4 * NGL : 0) <= BS;  // (exact: the LDG range runs in D0)
-  static constexpr int OF = WIDE ? OFa : Q, OG = WIDE ? OGa : (SLATE ? Q : OF + 4 * NQ), OL = OG + P,
+  static constexpr int OF = WIDE ? OFa : Q, OG = WIDE ? OGa : (SLIM ? Q : OF + 4 * NQ), OL = OG + P,
                        WEND = OL + 4 * NGL, BEND = OL;
   // FPRE (exact): A2 also interpolates each face's own-side traces and, on physical
   // boundaries, the ghost-side traces to the face quad points, into s_fi [8][4*NQ] (in the
   // W region, dead from A to D0), so B's face fluxes interpolate only the neighbour traces
-  static constexpr bool FPRE = !SF && !SLATE && (LEAN || 4 * NQ * 8 <= QN_END_W);
+  static constexpr bool FPRE = !SF && !SLIM && (LEAN || 4 * NQ * 8 <= W_END - O_W);
   static constexpr int WTMAX = QC * NGL;  // term tasks of a full chunk
   // VSUM (exact, chunked D): a chunk's term tasks split in two node halves on threads
   // [0, 2*WTMAX) (the longest lane forms ceil(NGL/2) nodes' terms instead of NGL), and the 3P
@@ -309,7 +306,7 @@ struct StageCfg {
   // phase, the partial sum in a register (instead of 3 chains per thread through s_rhs); qq and
   // the LDG face fluxes (D0, no sums yet) after the terms
   static constexpr int OVS = BS - 3 * P;
-  static constexpr bool VSUM = !SF && !OTF && 2 * WTMAX <= OVS &&
+  static constexpr bool VSUM = !SF && !SLIM && 2 * WTMAX <= OVS &&
                                2 * WTMAX + P <= BS && OL >= 2 * WTMAX + P && OL + 4 * NGL <= BS;
   // NSPLIT: node groups of the term tasks (VSUM: two node halves), task t = (group t / WTMAX,
   // task t % WTMAX) on thread t.  (Measured, not kept: one group in the LEAN arenas, thirds, and the
@@ -317,7 +314,7 @@ struct StageCfg {
   static constexpr int NSPLIT = VSUM ? 2 : 1;
   // (LEAN: the rhs is written only in the last D phase, by the VSUM lanes)
   static_assert(!LEAN || (VSUM && TSZ >= 32 * NQ && TSZ >= 5 * P && 3 * P <= 64 * EW + 64), "LEAN layout");
-  static constexpr int TB_LAST = (NCH & 1) ? TB1 : TB0, TB_PREV = (NCH & 1) ? TB0 : TB1;
+  static constexpr int TB_LAST = (NCH & 1) ? 0 : TB0, TB_PREV = (NCH & 1) ? TB0 : 0;
   // REGACC (persistent sub-cycle): every accumulating task (quad point, face quad point, node,
   // LDG face node) has its own thread, the same in every stage, so the time averages can live in
   // that thread's registers for the whole launch and be written once, scaled, at the end
@@ -408,6 +405,22 @@ __device__ __forceinline__ void for_tasks(int tid, int o, int n, F &&f) {
   }
 }
 
+// The ghost state of btp_extract_df behind a physical boundary (mod_barotropic_terms.F90:75-91) at
+// face node n, from the element's own state: its momentum (u, v) reflected about the wall normal
+// (er == -4; efn: the face's nodal statics) or negated (er == -2), otherwise unchanged.
+template <int NGL>
+__device__ __forceinline__ void wall_ghost(int er, const double *efn, int n, double &u, double &v) {
+  if (er == -4) {
+    const double nxn = efn[EFN_NX * NGL + n], nyn = efn[EFN_NY * NGL + n];
+    const double un = nxn * u + nyn * v;
+    u = u - 2.0 * un * nxn;
+    v = v - 2.0 * un * nyn;
+  } else if (er == -2) {
+    u = -u;
+    v = -v;
+  }
+}
+
 #define STAGE_MARK(k) \
   if (PROF && tid == 0) s_prof[k] = clock64();
 
@@ -429,14 +442,15 @@ __device__ __forceinline__ void for_tasks(int tid, int o, int n, F &&f) {
 // (C4 1264-1273 -> 1249-1255 us per stage, lake200 516 -> 508, same bits: profiles/r06/ab_accf.log.
 // The scratch-loaded bottom-layer qprime of the later stages fixed the same way measured slower,
 // 1252 -> 1261-1264 us, and is not kept.)
-// FST: whether this is a sub-cycle's first stage fixed at compile time (1 first, 2 a later one; 0:
-// the argument first_rt decides).
+// FST: the persistent sub-cycle's stage position, fixed at compile time (1 its first stage, 2 a later
+// one; 0: the per-stage kernel, every launch of which loads everything as a first stage does).
 template <int NGL, int NQ, bool SF, bool PERSIST, class ARGS, int NB = 0, int ACCF = 0, int FST = 0>
 __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsigned long long *s_prof,
-                                           bool first_rt, const int e, const int tid, unsigned long long ep = 0,
+                                           const int e, const int tid, unsigned long long ep = 0,
                                            double *pacc = nullptr) {
+  static_assert(PERSIST ? (FST == 1 || FST == 2) : FST == 0, "FST is the persistent stage position");
   const int accm = ACCF == 1 ? 2 : (ACCF == 2 ? 1 : a.accumulate);
-  const bool first = FST == 0 ? first_rt : FST == 1;
+  constexpr bool first = FST != 2;
   using C = StageCfg<NGL, NQ, SF, NB>;
   // persistent: the time averages accumulate in pacc (this thread's registers, see REGACC)
   constexpr bool REGACC = PERSIST && C::REGACC;
@@ -467,21 +481,20 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   double *s_wn = S + C::O_WN;      // [4][2][NGL] face-node normals (wall fix)
   double *s_qv = S + C::O_QV;      // [NQV][Q] (see StageCfg)
   double *s_pq = s_qv + 4 * Q;     // [3][Q] bottom-layer pp, up, vp (exact, A2 -> B)
-  // the quad-point values by role (StageCfg::QPM: quad-point-major): A2's interpolations c = 0..3
+  // the quad-point values by role (StageCfg::SLIM: quad-point-major): A2's interpolations c = 0..3
   // (dp, dpp, udp, vdp), the bottom layer's c = 0..2, B's outputs k = 0..6, the weight w, and the
   // metric pairs (QE_EX, QE_NX, QE_EY, QE_NY)
-  constexpr bool QPM = C::QPM;
-  // (QPM: slot sl of quad point q in pair-major order [4][Q][2] -- pair sl/2 of every quad point in one
+  // (SLIM: slot sl of quad point q in pair-major order [4][Q][2] -- pair sl/2 of every quad point in one
   // row: a writer lane q stores a 16-byte pair 16 B past its neighbour's, conflict-free, where the
   // record-per-quad-point order [Q][8] put the 16 lanes of a ds_write_b64 group 64 B apart on two bank
   // pairs, 8-way (C3: ~1,100 conflict cycles an element-stage); the on-the-fly sums still read the
   // four pairs of a quad point with one address and four immediate offsets)
   auto QSL = [&](int sl, int q) -> double & { return s_qv[((sl >> 1) * Q + q) * 2 + (sl & 1)]; };
-  auto QI = [&](int c, int q) -> double & { return QPM ? QSL(c, q) : s_qv[c * Q + q]; };
-  auto QP = [&](int c, int q) -> double & { return QPM ? QSL(4 + c, q) : s_pq[c * Q + q]; };
-  auto QO = [&](int k, int q) -> double & { return QPM ? QSL(1 + k, q) : s_qv[k * Q + q]; };
-  auto QW = [&](int q) -> double { return QPM ? QSL(0, q) : s_qk[qe_pos(QE_W, q, Q)]; };
-  auto QK = [&](int c, int q) -> double { return s_qk[qe_pos(c, q, Q) - (QPM ? Q : 0)]; };
+  auto QI = [&](int c, int q) -> double & { return C::SLIM ? QSL(c, q) : s_qv[c * Q + q]; };
+  auto QP = [&](int c, int q) -> double & { return C::SLIM ? QSL(4 + c, q) : s_pq[c * Q + q]; };
+  auto QO = [&](int k, int q) -> double & { return C::SLIM ? QSL(1 + k, q) : s_qv[k * Q + q]; };
+  auto QW = [&](int q) -> double { return C::SLIM ? QSL(0, q) : s_qk[qe_pos(QE_W, q, Q)]; };
+  auto QK = [&](int c, int q) -> double { return s_qk[qe_pos(c, q, Q) - (C::SLIM ? Q : 0)]; };
   double *s_y = S + C::O_Y;        // SF: [NYV][NGL][NQ] interpolation partials
   double *s_grad = S + C::O_GR, *s_qq = S + C::O_QQ;  // [4][P]
   // [4][4*NQ]: wq, flux, H_kx+flux_x, H_ky+flux_y at (face lf, quad iq) = lf*NQ + iq, component-major
@@ -517,14 +530,14 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   if (PROF && tid == 0 && (!PERSIST || first)) s_prof[22] = 0;
   const bool use_q0 = !a.rhs_only && a.a1 != 0.0, use_q2 = !a.rhs_only && a.a3 != 0.0;
   const int qpm = (SF || !m.botfr || !a.qpq) ? 0 : a.qpq_mode;  // see StageArgs::qpq
-  if (!DBGX(4096)) {
+  if (!DBG(4096)) {
     int rot = 0;
     const bool tsl = !PERSIST && m.etsrc && !a.tcontig;
     const int4 ts = tsl ? slot_ids4(m.etsrc + 4 * e) : make_int4(0, 0, 0, 0);
     if (!PERSIST || first) {
       glds_copy<BS, C::G16>(m.basis_pd, S + C::O_BASIS, 2 * C::NB, tid, rot);
       glds_copy<BS, C::G16>(m.erec + (size_t)e * C::ERS, S + C::O_EREC, C::ERS, tid, rot);
-      glds_copy<BS, C::G16>(m.qstatE + (size_t)e * qe_stride(Q) + (QPM ? Q : 0), s_qk, 2 * C::QKR * Q, tid, rot);
+      glds_copy<BS, C::G16>(m.qstatE + (size_t)e * qe_stride(Q) + (C::SLIM ? Q : 0), s_qk, 2 * C::QKR * Q, tid, rot);
       if constexpr (!C::SLIM) glds_copy<BS, C::G16>(a.ecoef + (size_t)e * C::ECO + 4 * Q, s_nc, 2 * 5 * P, tid, rot);
       glds_copy<BS, C::G16>(m.nstatE + (size_t)e * NE_N * P, s_ns, 2 * (C::SLIM ? NE_LDS : NE_N) * P, tid, rot);
     }
@@ -568,11 +581,11 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   // keeps the reference's summation order.)
   constexpr int NST = QE_N - QE_KEEP, NPRE = NST + 7;
   double pre[NPRE];
-  double r_wq = 0.0;  // (QPM: the quad task's weight, into s_qv slot 0 in B)
+  double r_wq = 0.0;  // (SLIM: the quad task's weight, into s_qv slot 0 in B)
   auto load_pre = [&]() {
     if (tid < Q) {
       const double *qse = m.qstatE + (size_t)e * qe_stride(Q) + tid;
-      if (QPM) r_wq = qse[0];  // (qe_pos(QE_W, q) = q)
+      if (C::SLIM) r_wq = qse[0];  // (qe_pos(QE_W, q) = q)
 #pragma unroll
       for (int k = 0; k < NST; k++) pre[k] = qse[(QE_KEEP + k) * Q];
       const double *eco = a.ecoef + (size_t)e * C::ECO + tid;
@@ -627,13 +640,13 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   // Y(var, mm, iq) = sum_n psiq(n, iq) X(var, n + mm*NGL), one thread per (group, mm, iq).
   // persistent: this thread's neighbour-trace granule is loaded now and checked after the
   // interpolation, so the hand-off latency hides behind it
-  constexpr bool GR1 = 32 * NGL <= BS;  // at most one granule per thread
+  static_assert(32 * NGL <= BS, "at most one granule per thread (issue_granule, poll_traces)");
   granule_u4 gx = {0u, 0u, 0u, 0u};
   bool gwant = false;
-  // issue this thread's granule load (GR1) now; poll_traces checks it and polls again while
+  // issue this thread's granule load now; poll_traces checks it and polls again while
   // it is older than this stage
   auto issue_granule = [&]() {
-    if constexpr (PERSIST && GR1) {
+    if constexpr (PERSIST) {
       if (tid < 32 * NGL) {
         gwant = s_bc[tid / (8 * NGL)] > 0;  // interior face: a neighbour writes this slot
         if (gwant) {
@@ -646,22 +659,16 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       }
     }
   };
+  // (its poll loop and poll_wave's are two copies: shared, dg25L3 persistent measured 10.58 -> 10.68 us per stage)
   auto poll_traces = [&]() {
     if constexpr (PERSIST) {
       const unsigned long long want = (ep << 20) | a.tag_in;
       const unsigned long long c0 = PROF ? clock64() : 0;
       for (int t = tid; t < 32 * NGL; t += BS) {
-        bool w_ = GR1 ? gwant : s_bc[t / (8 * NGL)] > 0;
-        if (!w_) continue;
+        if (!gwant) continue;
         const TraceGranule *g = a.gtr_in + (size_t)e * 32 * NGL + t;
-        double v;
-        unsigned long long tag;
-        if (GR1) {
-          v = __builtin_bit_cast(double, ((unsigned long long)gx[1] << 32) | gx[0]);
-          tag = ((unsigned long long)gx[3] << 32) | gx[2];
-        } else {
-          ld_granule(g, v, tag);
-        }
+        double v = __builtin_bit_cast(double, ((unsigned long long)gx[1] << 32) | gx[0]);
+        unsigned long long tag = ((unsigned long long)gx[3] << 32) | gx[2];
         unsigned spins = 0;
         while (tag != want && !DBG(16)) {
           __builtin_amdgcn_s_sleep(1);
@@ -676,11 +683,11 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       if (PROF) atomicMax(&s_prof[22], clock64() - c0);  // longest trace wait of the stage
     }
   };
-  // SLATE: the last wave loads every granule of the element (NGR per lane) and checks them in D
+  // SLIM: the last wave loads every granule of the element (NGR per lane) and checks them in D
   // (poll_wave), before the face fluxes it runs there
   granule_u4 gxr[C::NGR];
   auto issue_granules_wave = [&]() {
-    if constexpr (PERSIST && C::SLATE) {
+    if constexpr (PERSIST && C::SLIM) {
       if (tid >= BS - 64) {
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
             (void *)(a.gtr_in + (size_t)e * 32 * NGL), 0, 32 * NGL * (int)sizeof(TraceGranule), 0x00020000);
@@ -691,7 +698,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     }
   };
   auto poll_wave = [&]() {
-    if constexpr (PERSIST && C::SLATE) {
+    if constexpr (PERSIST && C::SLIM) {
       const unsigned long long want = (ep << 20) | a.tag_in;
       const unsigned long long c0 = PROF ? clock64() : 0;
 #pragma unroll
@@ -714,7 +721,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       if (PROF) atomicMax(&s_prof[22], clock64() - c0);
     }
   };
-  if constexpr (!C::SLATE) issue_granule();
+  if constexpr (!C::SLIM) issue_granule();
   {
     // persistent, after the first stage: the wall normals and u_bar, v_bar of this state are in
     // LDS already (E1 formed u_bar, v_bar of the new state); qpm == 2: pp, up, vp are loaded
@@ -730,7 +737,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     for (int w = tid; w < T_UV + NFP; w += BS) {
       asm volatile("" ::: "memory");
       if (w < nint) {
-        if (DBGX(128)) continue;
+        if (DBG(128)) continue;
         const int g = w / TPG, r = w % TPG;
         if constexpr (SF) {
           const int mm = r / NQ, iq = r % NQ;
@@ -871,17 +878,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
             const int p = s_map[lf * NGL + n];
 #pragma unroll
             for (int c = 0; c < 4; c++) x[c][n] = s_qb[p * 4 + c];
-            if (part == 1) {
-              if (er == -4) {
-                const double nxn = efn[EFN_NX * NGL + n], nyn = efn[EFN_NY * NGL + n];
-                const double un = nxn * x[2][n] + nyn * x[3][n];
-                x[2][n] = x[2][n] - 2.0 * un * nxn;
-                x[3][n] = x[3][n] - 2.0 * un * nyn;
-              } else if (er == -2) {
-                x[2][n] = -x[2][n];
-                x[3][n] = -x[3][n];
-              }
-            }
+            if (part == 1) wall_ghost<NGL>(er, efn, n, x[2][n], x[3][n]);
           }
           double acc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -908,6 +905,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
         for (int c = 0; c < 4; c++) s_grad[c * P + p] = g[c];
       }
       LDS_BARRIER();
+      // (E2's scatter from the input state, a copy: shared, it measured slower -- the figures are at sum_last_v)
       for (int t = tid; t < 4 * 8 * NGL; t += BS) {
         const int lf = t / (8 * NGL), c = (t / NGL) % 8, n = t % NGL;
         if (s_bc[lf] < 0) continue;
@@ -918,7 +916,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       }
     }
   }
-  if constexpr (!C::SLATE) poll_traces();  // (the granule was issued before the interpolation)
+  if constexpr (!C::SLIM) poll_traces();  // (the granule was issued before the interpolation)
   LDS_BARRIER();
   STAGE_MARK(1);
 
@@ -973,18 +971,9 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
 #pragma unroll
         for (int c = 0; c < 4; c++) oth[c] = tr[c * NGL + n];
       } else {
-        // ghost state of btp_extract_df (mod_barotropic_terms.F90:75-91)
 #pragma unroll
         for (int c = 0; c < 4; c++) oth[c] = own[c];
-        if (er == -4) {
-          const double nxn = efn[EFN_NX * NGL + n], nyn = efn[EFN_NY * NGL + n];
-          const double un = nxn * own[2] + nyn * own[3];
-          oth[2] = own[2] - 2.0 * un * nxn;
-          oth[3] = own[3] - 2.0 * un * nyn;
-        } else if (er == -2) {
-          oth[2] = -own[2];
-          oth[3] = -own[3];
-        }
+        wall_ghost<NGL>(er, efn, n, oth[2], oth[3]);
       }
 #pragma unroll
       for (int c = 0; c < 4; c++) {
@@ -1043,7 +1032,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   for (int w = tid; w < C::BEND; w += BS) {
     asm volatile("" ::: "memory");
     if (w < Q) {
-      if (DBGX(256)) continue;
+      if (DBG(256)) continue;
       // ---- quad-point physics (mod_rhs_btp.F90:136-192)
       const int q = w, iq = q % NQ, jq = q / NQ;
       double dp = 0, dpp = 0, udp = 0, vdp = 0, pp = 0, up = 0, vp = 0;
@@ -1143,7 +1132,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
         s_qv[6 * Q + q] = wq * (nx * A + ny * quv);
         s_qv[7 * Q + q] = wq * (nx * quv + ny * B);
       } else {
-        if (QPM) QSL(0, q) = r_wq;
+        if (C::SLIM) QSL(0, q) = r_wq;
         QO(0, q) = udp;
         QO(1, q) = vdp;
         QO(2, q) = sc_x;
@@ -1152,10 +1141,10 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
         QO(5, q) = sc_y;
         QO(6, q) = Hq + qv;
       }
-    } else if (!C::SLATE && w >= C::OF && w < C::OF + 4 * NQ) {
-      if (!DBGX(512)) face_task(w - C::OF);
+    } else if (!C::SLIM && w >= C::OF && w < C::OF + 4 * NQ) {
+      if (!DBG(512)) face_task(w - C::OF);
     } else if (w >= C::OG && w < C::OL) {
-      if (DBGX(1024)) continue;
+      if (DBG(1024)) continue;
       const int p = w - C::OG, i = p % NGL, j = p / NGL;
       double g[4];
       if (PERSIST && (!first || a.self_trace)) {  // formed by the previous stage's E2 (or A2) for this state
@@ -1202,6 +1191,31 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       const double *fq = s_fq + lf * NQ;
 #pragma unroll
       for (int iq = 0; iq < NQ; iq++) acc = acc + sg * (fq[iq] * PSQ(n * NQ + iq) * fq[(1 + v) * FQS + iq]);
+    }
+    return acc;
+  };
+  // the same projection for the chunked sums' chains, batched: a face's NQ points are loaded before
+  // its adds, and acc - c is formed as acc + (-c) (exact) so only the adds sit on the dependent
+  // chain.  (face_proj's order of operations, another load batching: kept apart.)
+  auto lift_faces = [&](int v, int p, double acc) {
+#pragma unroll
+    for (int kf = 0; kf < 2; kf++) {
+      asm volatile("" ::: "memory");
+      const int r = s_pf[2 * p + kf];
+      if (r < 0) continue;
+      const int lf = r / NGL, n = r % NGL;
+      const double sg = s_side[lf] == 0 ? -1.0 : 1.0;
+      const double *fq = s_fq + lf * NQ;
+      double c[NQ], fw[NQ], ps[NQ];
+#pragma unroll
+      for (int iq = 0; iq < NQ; iq++) {
+        fw[iq] = fq[iq];
+        ps[iq] = PSQ(n * NQ + iq);
+        c[iq] = fq[(1 + v) * FQS + iq];
+      }
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int iq = 0; iq < NQ; iq++) acc = acc + sg * ((fw[iq] * ps[iq]) * c[iq]);
     }
     return acc;
   };
@@ -1371,15 +1385,15 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     }
     LDS_BARRIER();
     STAGE_MARK(7);
-  } else if constexpr (C::OTF) {
-    // D (OTF): rhs(v,p) = sum_q T(v,p,q) summed in quad order by one thread, each term computed
+  } else if constexpr (C::SLIM) {
+    // D (SLIM, on the fly): rhs(v,p) = sum_q T(v,p,q) summed in quad order by one thread, each term computed
     // as it goes (create_rhs_btp_volume_qdf, mod_rhs_btp.F90:194-206):
     //   T(0) = wq*(dhdx*udp + dhdy*vdp), T(1) = wq*(hi*scx + dhdx*A + quv*dhdy),
     //   T(2) = wq*(hi*scy + dhdx*quv + dhdy*B)
     // Then the face projections; qq and the LDG face fluxes run beside; the Laplacian after the
     // barrier.  (quad-point values by role: QO(k, q), k = 0..6 = udp, vdp, scx, A, quv, scy, B; QW,
-    // QK -- see QPM)
-    // OPAIR: node p's component-0 sum on one thread (without the zero hi*s1 term: the
+    // QK -- see StageCfg::SLIM)
+    // Per-stage kernel: node p's component-0 sum on one thread (without the zero hi*s1 term: the
     // reference's own wq*(dhdx*udp + dhdy*vdp)), its component-1 and -2 sums together on
     // another, sharing hi, dhdx, dhdy -- 36 instead of 48 f64 operations per (p, q), the same
     // terms in the same order
@@ -1474,7 +1488,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
             s_rhs[2 * P + tid] = a2_;
           }
           if (PROF && tid == 0) s_prof[28] = clock64();
-        } else {  // (OPAIR: component 0 on wave 0, components 1 and 2 together on wave 1)
+        } else {  // (component 0 on wave 0, components 1 and 2 together on wave 1)
           if (tid < P)
             acc_r = otf_sum0(tid);
           else if (tid >= 64 && tid < 64 + P)
@@ -1506,7 +1520,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
 #pragma unroll
           for (int c = 0; c < 4; c++) s_qq[c * P + p] = nc[NC_PV] * s_grad[c * P + p] + nc[NC_D1 + c];
         }
-        // the neighbour traces (persistent: checked now), then the face fluxes (SLATE)
+        // the neighbour traces (persistent: checked now), then the face fluxes
         issue_granules_wave();
         poll_wave();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1550,7 +1564,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     // wq*(...)) while chunk k-1 is summed in quad order by one thread per (v,p); qq rides in
     // D0, the Laplacian in the last phase.
     // term task (q in chunk k, i): T(v, p=(i,j), q) for j = 0..NGL-1
-    auto tbuf = [&](int k) { return SB + ((k & 1) ? C::TB1 : C::TB0); };
+    auto tbuf = [&](int k) { return SB + ((k & 1) ? 0 : C::TB0); };
     // (VSUM: task t >= WTMAX is the second node half of pair t - WTMAX: j from JH on; the halves
     // run the same code, the second's surplus iteration masked)
     constexpr bool VSUM = C::VSUM;
@@ -1559,9 +1573,10 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     // row offset are the same in every phase, so they are formed once, before the phases, and the
     // per-phase LDS addresses are one per-lane base plus the phase's constant (immediate offsets)
     constexpr bool FULLCH = (Q % QC == 0) && (QC % NQ == 0) && C::WTMAX * NSP <= BS;  // (task t on thread t)
+    static_assert(NSP <= 2, "a term task's node group is t >= WTMAX");
     int tl_i = 0, tl_qi = 0, tl_iq = 0, tl_jr = 0;
     if constexpr (FULLCH) {
-      const int h = NSP == 2 ? (tid >= C::WTMAX ? 1 : 0) : (NSP > 1 ? tid / C::WTMAX : 0), tq = tid - h * C::WTMAX;
+      const int h = NSP == 2 ? (tid >= C::WTMAX ? 1 : 0) : 0, tq = tid - h * C::WTMAX;
       tl_i = tq / QC;
       tl_qi = tq - tl_i * QC;
       tl_iq = (QC == NQ) ? tl_qi : tl_qi % NQ;
@@ -1569,7 +1584,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     }
     auto term_task = [&](int k, int t) {
       double *T = tbuf(k);
-      const int h = NSP == 2 ? (t >= C::WTMAX ? 1 : 0) : (NSP > 1 ? t / C::WTMAX : 0), tq = t - h * C::WTMAX;
+      const int h = NSP == 2 ? (t >= C::WTMAX ? 1 : 0) : 0, tq = t - h * C::WTMAX;
       // task tq = i*nq_k + qi: consecutive lanes write consecutive quad points of one node's row
       // of the term buffer (pitch QCP = QC | 1), so a wave's ds_write_b64 lanes hit distinct banks
       // (qi-major, the lanes were QCP doubles apart: 2-way conflicts)
@@ -1599,9 +1614,9 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       }
     };
     // sum task (p): rhs(v,p) += T(v,p,q) over chunk k in quad order for v = 0..2 (three
-    // independent ordered chains); the face projections after the last chunk
+    // independent ordered chains), for every chunk but the last (whole: QC points), which
+    // sum_last_v sums and lifts
     auto sum_task = [&](int k, int p) {
-      const int nq_k = (k == NCH - 1) ? Q - k * QC : QC;
       double acc[3];
 #pragma unroll
       for (int v = 0; v < 3; v++) acc[v] = k == 0 ? 0.0 : s_rhs[v * P + p];
@@ -1615,54 +1630,20 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
 #pragma unroll
         for (int qi = q0; qi < q0 + SBK && qi < QC; qi++)
 #pragma unroll
-          for (int v = 0; v < 3; v++) tv[v][qi - q0] = qi < nq_k ? T[v * P * QCP + qi] : 0.0;
+          for (int v = 0; v < 3; v++) tv[v][qi - q0] = T[v * P * QCP + qi];
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int qi = q0; qi < q0 + SBK && qi < QC; qi++)
-          if (qi < nq_k) {
 #pragma unroll
-            for (int v = 0; v < 3; v++) acc[v] = acc[v] + tv[v][qi - q0];
-          }
-      }
-      if (k == NCH - 1 && !DBG(1)) {
-        // face projections of the three components, each in the reference order; a face's
-        // NQ points are loaded as one batch, and acc - c is formed as acc + (-c) (exact) so
-        // only the adds sit on the dependent chain
-#pragma unroll
-        for (int kf = 0; kf < 2; kf++) {
-          asm volatile("" ::: "memory");
-          const int r = s_pf[2 * p + kf];
-          if (r < 0) continue;
-          const int lf = r / NGL, n = r % NGL;
-          const double sg = s_side[lf] == 0 ? -1.0 : 1.0;
-          const double *fq = s_fq + lf * NQ;
-          constexpr int FB = (NQ + 1) / 2;  // points per load batch
-#pragma unroll
-          for (int i0 = 0; i0 < NQ; i0 += FB) {
-            double c[3][FB], fw[FB], ps[FB];
-#pragma unroll
-            for (int iq = i0; iq < i0 + FB && iq < NQ; iq++) {
-              fw[iq - i0] = fq[iq];
-              ps[iq - i0] = PSQ(n * NQ + iq);
-#pragma unroll
-              for (int v = 0; v < 3; v++) c[v][iq - i0] = fq[(1 + v) * FQS + iq];
-            }
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int iq = i0; iq < i0 + FB && iq < NQ; iq++) {
-              const double wp = fw[iq - i0] * ps[iq - i0];
-#pragma unroll
-              for (int v = 0; v < 3; v++) acc[v] = acc[v] + sg * (wp * c[v][iq - i0]);
-            }
-          }
-        }
+          for (int v = 0; v < 3; v++) acc[v] = acc[v] + tv[v][qi - q0];
       }
 #pragma unroll
       for (int v = 0; v < 3; v++) s_rhs[v * P + p] = acc[v];
     };
-    // the last chunk, one thread per (v, p) (one chain each, a third of the face-lift chain of
-    // sum_task): rhs(v,p) += T(v,p,q) over the chunk, then the face projections of component v,
-    // the same adds in the same order as sum_task
+    // the last chunk, one thread per (v, p) (one chain each): rhs(v,p) += T(v,p,q) over the chunk,
+    // then the face projections of component v
+    // (the blocked sum is vsum_chunk's, a copy: shared, and with one scatter for A2's and E2's traces, the
+    // persistent stage measured dg25L3 10.57 -> 10.63 us, dg25N7L3 35.43 -> 36.05 us)
     auto sum_last_v = [&](int v, int p) {
       constexpr int kc = NCH - 1, nq_k = Q - kc * QC;
       double acc = kc == 0 ? 0.0 : s_rhs[v * P + p];
@@ -1678,39 +1659,18 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
         for (int qi = 0; qi < SBK; qi++)
           if (q0 + qi < nq_k) acc = acc + tv[qi];
       }
-      if (!DBG(1)) {
-#pragma unroll
-        for (int kf = 0; kf < 2; kf++) {
-          asm volatile("" ::: "memory");
-          const int r = s_pf[2 * p + kf];
-          if (r < 0) continue;
-          const int lf = r / NGL, n = r % NGL;
-          const double sg = s_side[lf] == 0 ? -1.0 : 1.0;
-          const double *fq = s_fq + lf * NQ;
-          double c[NQ], fw[NQ], ps[NQ];
-#pragma unroll
-          for (int iq = 0; iq < NQ; iq++) {
-            fw[iq] = fq[iq];
-            ps[iq] = PSQ(n * NQ + iq);
-            c[iq] = fq[(1 + v) * FQS + iq];
-          }
-          asm volatile("" ::: "memory");
-#pragma unroll
-          for (int iq = 0; iq < NQ; iq++) acc = acc + sg * ((fw[iq] * ps[iq]) * c[iq]);
-        }
-      }
+      if (!DBG(1)) acc = lift_faces(v, p, acc);
       s_rhs[v * P + p] = acc;
     };
     // (the Laplacian from thread 0 in the last phase, these after it)
     constexpr int OSV = ((2 * P + 63) / 64) * 64;
-    constexpr bool VSPLIT = OSV + 3 * P <= BS;
+    static_assert(VSUM || OSV + 3 * P <= BS, "sum_last_v: one thread per chain, behind the Laplacian's");
     // lanes: terms from 0, the sums on the last wave when they fit beside the terms, qq
     // after the terms (D0), the Laplacian from 0 in the last phase (no terms there); the face
     // fluxes ran in B, the LDG fluxes run in D0
     constexpr int WTMAX = C::WTMAX;
     constexpr int OSUM = (P <= 64 && WTMAX <= BS - 64) ? BS - 64 : WTMAX;
     // VSUM: thread OVS + (v*P + p) sums chain (v, p) of every chunk, the partial sum in vacc
-    // (VPACK: chain tid - VCH_HI on the last wave, 64 + tid - VCH_LO on wave 1)
     const int vch = tid >= C::OVS ? tid - C::OVS : -1;
     double vacc = 0.0;
     auto vsum_chunk = [&](int k) {
@@ -1729,27 +1689,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
           if (q0 + qi < nq_k) vacc = vacc + tv[qi];
       }
       if (k == NCH - 1) {
-        if (!DBG(1)) {  // the face projections of component v (sum_last_v's)
-#pragma unroll
-          for (int kf = 0; kf < 2; kf++) {
-            asm volatile("" ::: "memory");
-            const int r = s_pf[2 * p + kf];
-            if (r < 0) continue;
-            const int lf = r / NGL, n = r % NGL;
-            const double sg = s_side[lf] == 0 ? -1.0 : 1.0;
-            const double *fq = s_fq + lf * NQ;
-            double c[NQ], fw[NQ], ps[NQ];
-#pragma unroll
-            for (int iq = 0; iq < NQ; iq++) {
-              fw[iq] = fq[iq];
-              ps[iq] = PSQ(n * NQ + iq);
-              c[iq] = fq[(1 + v) * FQS + iq];
-            }
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int iq = 0; iq < NQ; iq++) vacc = vacc + sg * ((fw[iq] * ps[iq]) * c[iq]);
-          }
-        }
+        if (!DBG(1)) vacc = lift_faces(v, p, vacc);
         s_rhs[v * P + p] = vacc;
       }
     };
@@ -1773,19 +1713,12 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       const int WT = (k < NCH) ? ((k == NCH - 1) ? (Q - k * QC) : QC) * NGL : 0;  // term tasks
       if constexpr (VSUM) {
         // first node halves on [0, WT), second halves on [WTMAX, WTMAX + WT)
-        if ((NSP == 2 ? (tid < WT || (tid >= WTMAX && tid < WTMAX + WT))
-                      : (tid < NSP * WTMAX && tid - (tid / WTMAX) * WTMAX < WT)) && !DBG(64))
-          term_task(k, tid);
+        if ((tid < WT || (tid >= WTMAX && tid < WTMAX + WT)) && !DBG(64)) term_task(k, tid);
         if (k >= 1 && vch >= 0 && !DBG(4)) vsum_chunk(k - 1);
       } else {
       for_tasks<BS>(tid, 0, WT, [&](int t, bool) { term_task(k, t); });
       if (k >= 1 && k < NCH) for_tasks<BS>(tid, OSUM, P, [&](int t, bool) { sum_task(k - 1, t); });
-      if (k == NCH && !DBG(4)) {
-        if constexpr (VSPLIT)
-          for_tasks<BS>(tid, OSV, 3 * P, [&](int t, bool) { sum_last_v(t / P, t % P); });
-        else
-          for_tasks<BS>(tid, OSUM, P, [&](int t, bool) { sum_task(k - 1, t); });
-      }
+      if (k == NCH && !DBG(4)) for_tasks<BS>(tid, OSV, 3 * P, [&](int t, bool) { sum_last_v(t / P, t % P); });
       }
       if (k == 0) for_tasks<BS>(tid, VSUM ? C::NSPLIT * WTMAX : WT, P, [&](int t, bool) { qq_task(t); });
       if (k == 0) for_tasks<BS>(tid, C::OL, 4 * NGL, ldg_task);
@@ -1909,7 +1842,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   // (persistent: the state stays in LDS; only the sub-cycle's last stage writes it out)
   if (!PERSIST || !a.write_trace)
     for (int t = tid; t < 4 * P; t += BS) a.qb_out[(size_t)e * 4 * P + t] = s_qn[t];
-  if (a.write_trace && !DBGX(2048)) {
+  if (a.write_trace && !DBG(2048)) {
     // traces of the new state on each interior face, into the neighbour's slot:
     // qb(4) and grad(u_bar)(4) at the face nodes
     for (int t = tid; t < 4 * 8 * NGL; t += BS) {
@@ -1956,12 +1889,12 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     if (tid == 0) {
       if (PERSIST) {  // sums over the stages: A incl. the trace waits | the rest | stages
         if (first) s_prof[24] = s_prof[25] = s_prof[26] = s_prof[27] = s_prof[8] = s_prof[9] = s_prof[10] = s_prof[11] = s_prof[29] = 0;
-        // per-phase sums over the stages: A2 | B | D | E, and (SLATE) the volume sums of wave 0
+        // per-phase sums over the stages: A2 | B | D | E, and (SLIM) the volume sums of wave 0
         s_prof[8] += s_prof[1] - s_prof[21];
         s_prof[9] += s_prof[2] - s_prof[1];
         s_prof[10] += s_prof[3] - s_prof[2];
         s_prof[11] += s_prof[5] - s_prof[3];
-        if (C::SLATE) s_prof[29] += s_prof[28] - s_prof[2];
+        if (C::SLIM) s_prof[29] += s_prof[28] - s_prof[2];
         s_prof[27] += s_prof[22];
         s_prof[24] += s_prof[21] - s_prof[0];
         s_prof[25] += s_prof[5] - s_prof[21];
@@ -1979,7 +1912,7 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF, NB>::BS), (StageCfg<NGL
     btp_stage_kernel(StageArgs a) {
   __shared__ __attribute__((aligned(16))) double s_arena[StageCfg<NGL, NQ, SF, NB>::ARENA];
   __shared__ unsigned long long s_prof[HNUMO_DIAG ? 32 : 1];
-  stage_body<NGL, NQ, SF, false, StageArgs, NB, ACCF>(a, s_arena, s_prof, true,
+  stage_body<NGL, NQ, SF, false, StageArgs, NB, ACCF>(a, s_arena, s_prof,
                                                       a.elist ? a.elist[blockIdx.x] : (int)blockIdx.x, threadIdx.x);
 }
 
@@ -2072,7 +2005,7 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
     int tid_s = tid, e_s = e;
     asm volatile("" : "+v"(tid_s), "+s"(e_s));
     tid_s &= C::BS - 1;
-    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 1>(tab[0], s_arena, s_prof, true, e_s, tid_s, ep, pacc);
+    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 1>(tab[0], s_arena, s_prof, e_s, tid_s, ep, pacc);
   }
 #pragma unroll 1
   for (int stage = 1; stage < NS; stage++) {
@@ -2089,7 +2022,7 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
     int tid_s = tid, e_s = e;
     asm volatile("" : "+v"(tid_s), "+s"(e_s));
     tid_s &= C::BS - 1;  // restore the known range of the thread index
-    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 2>(tab[stage], s_arena, s_prof, false, e_s, tid_s, ep, pacc);
+    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 2>(tab[stage], s_arena, s_prof, e_s, tid_s, ep, pacc);
   }
   // the next launch's tags: every workgroup read the epoch at its start, so the last one to
   // finish (agent-scope counter) moves it on and resets the counters (every workgroup has passed
@@ -2105,11 +2038,10 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
 }
 
 // Face traces of a state for the first stage of a sub-cycle / a lone RHS: qb(4) and
-// grad(u_bar)(4) at the face nodes, written into the neighbours' trace slots (or, with gtr,
-// as tagged granules for the persistent sub-cycle).
+// grad(u_bar)(4) at the face nodes, written into the neighbours' trace slots.  (The persistent
+// sub-cycle's stage 0 publishes its own: StageArgs::self_trace.)
 template <int NGL, int NQ>
-__global__ void __launch_bounds__(64) grad_trace_kernel(DevMesh m, const double *qb, double *trace, int e0,
-                                                         TraceGranule *gtr, const unsigned long long *epoch) {
+__global__ void __launch_bounds__(64) grad_trace_kernel(DevMesh m, const double *qb, double *trace, int e0) {
   constexpr int P = NGL * NGL, ERS = EREC_SIZE(NGL);
   const int e = e0 + blockIdx.x, tid = threadIdx.x;
   __shared__ double s_dpsi[NGL * NGL + 1], s_qb[P * 4], s_nm[4 * P], s_u[P], s_v[P];
@@ -2138,10 +2070,7 @@ __global__ void __launch_bounds__(64) grad_trace_kernel(DevMesh m, const double 
       val = nodal_grad<NGL>(s_dpsi, i, j, ex, nx, (cg >> 1) ? s_v : s_u);
     }
     const size_t slot = (((size_t)s_er[EREC_NBE + lf] * 4 + s_er[EREC_NBLF + lf]) * 8 + c) * NGL + n;
-    if (gtr)  // persistent sub-cycle: tagged for its stage 0
-      st_granule(gtr + slot, val, (*epoch << 20) | 1ull);
-    else
-      trace[slot] = val;
+    trace[slot] = val;
   }
 }
 
@@ -2173,7 +2102,6 @@ __global__ void btp_finalize_kernel(double *qacc, double *facc, double *nacc, do
   template __global__ void btp_stage_kernel<NGL, NQ, true>(StageArgs);  \
   template __global__ void btp_subcycle_kernel<NGL, NQ, false>(SubArgs); \
   template __global__ void btp_subcycle_kernel<NGL, NQ, true>(SubArgs);  \
-  template __global__ void grad_trace_kernel<NGL, NQ>(DevMesh, const double *, double *, int, TraceGranule *, \
-                                                       const unsigned long long *);
+  template __global__ void grad_trace_kernel<NGL, NQ>(DevMesh, const double *, double *, int);
 
 }  // namespace hnumo

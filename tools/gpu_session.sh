@@ -12,7 +12,6 @@
 #   benchq       the full bench line without the CPU baselines
 #   emu8         bench.py --emulate 8:1 (C4 rank 1 of 8) under torch.distributed.run, one process
 #   emu4lake     bench.py --emulate 4:1 --config lake200 (C5 rank 1 of 4) the same way
-#   nb56         tools/ab_env.py: C4 per-stage kernel, LEAN arena for 5 vs 6 workgroups per CU
 #   sprof:<cfg>  tools/stage_profile.py with the diagnostics build diag/libhnumo_diag.so (phase clocks)
 #   bclprof:<cfg>  tools/bcl_profile.py with the diagnostics build (element kernels' phase clocks)
 #   abbd:<cfg[:stage]>:<KNOB>:<v1>/<v2>  tools/ab_breakdown.py (per-kernel step breakdown per value)
@@ -64,9 +63,6 @@ for step in "$@"; do
     emu4lake2)
       timeout -k 10 600 $TR bench.py --emulate 4:1 --config lake200 --warmup 1 --steps 2 > $O/emu4lake2.json 2> $O/emu4lake2.err || fail "$step" $? $O/emu4lake2.err
       cat $O/emu4lake2.json ;;
-    nb56)
-      AB_REPS=2 timeout -k 10 600 python -u tools/ab_env.py dg316L3:stage HNUMO_STAGE_NB=5 HNUMO_STAGE_NB=6 > $O/nb56.log 2>&1 || fail "$step" $? $O/nb56.log
-      cat $O/nb56.log ;;
     sprof:*)
       c=${step#sprof:}
       HNUMO_LIB=diag/libhnumo_diag.so timeout -k 10 300 python -u tools/stage_profile.py $c > $O/sprof_$c.txt 2>&1 || fail "$step" $? $O/sprof_$c.txt
