@@ -25,11 +25,13 @@
 #include "../../include/hnumo_engine.h"
 #include "engine_internal.h"
 #include "setup_plan.h"
+#include "sample_plan.h"
 #include "kernels_bcl.hip"
 #include "kernels_btp.hip"
 #include "kernels_lapq.hip"
 #include "kernels_diag.hip"
 #include "kernels_stats.hip"
+#include "kernels_sample.hip"
 
 using namespace hnumo;
 
@@ -194,6 +196,20 @@ struct hnumo_engine {
   double *st_sums = nullptr, *st_part = nullptr, *st_tree[2] = {nullptr, nullptr}, *st_series = nullptr;
   int st_every = 0, st_cap = 0, st_count = 0;
   int64_t st_nsamples = 0, st_steps = 0;
+  // sample sets (kernels_sample.hip; hnumo_sample_*): the host plan (sample_plan.h), its tables on
+  // the device, one sample's output [V][M] and the series [capacity][V][M]; series entries held,
+  // successful steps since hnumo_sample_series_begin (every > 0: the engine records after every
+  // every-th one)
+  struct SampleSet {
+    bool used = false;
+    int source = 0, V = 0;
+    SamplePlan plan;
+    int *d_tab = nullptr;                  // chunk_pt | chunk_el | el_list | slot | perm
+    const int *d_chunk_pt = nullptr, *d_chunk_el = nullptr, *d_el_list = nullptr, *d_slot = nullptr, *d_perm = nullptr;
+    double *d_w = nullptr, *d_out = nullptr, *d_series = nullptr;
+    int every = 0, cap = 0, count = 0;
+    int64_t steps = 0;
+  } samples[SP_MAXSETS];
 };
 
 // the per-kernel breakdown's mark after a launch on the engine stream (no-op outside
@@ -1322,6 +1338,7 @@ int hnumo_overrides(const hnumo_engine *eng, char *out, int64_t len) {
 const char *hnumo_last_error(const hnumo_engine *eng) { return eng ? eng->err.c_str() : "null engine"; }
 
 static void stats_free(hnumo_engine *eng);
+static void sample_free(hnumo_engine *eng, int id);
 
 void hnumo_engine_destroy(hnumo_engine *eng) {
   if (!eng) return;
@@ -1333,6 +1350,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   if (eng->h_steps) (void)hipHostFree(eng->h_steps);
   if (eng->h_diag) (void)hipHostFree(eng->h_diag);
   stats_free(eng);
+  for (int id = 0; id < SP_MAXSETS; id++) sample_free(eng, id);
   if (eng->stream && eng->own_stream) (void)hipStreamDestroy(eng->stream);
   if (LocalGroup *g = eng->group) {
     // the destroyed engine cannot take part in exchanges any more; the last one out frees
@@ -1563,6 +1581,9 @@ static int component_transport_check(hnumo_engine *eng) {
 // the flow statistics' sample after a successful step (hnumo_stats_begin with every >= 1; a no-op
 // otherwise): after run_steps returned 0, so a step redone on per-stage launches is sampled once
 static int stats_after_step(hnumo_engine *eng);
+// the sample sets' series after a successful step (hnumo_sample_series_begin with every >= 1): after
+// the statistics' own sample of the step, so a set on the statistics sees the new sums
+static int sample_after_step(hnumo_engine *eng);
 
 int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime_df) {
   if (!eng) return HNUMO_ERR_INVALID;
@@ -1576,7 +1597,9 @@ int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qpri
   int rc = run_steps(eng, 1);
   if (rc) return rc;
   if (!eng->resident && (rc = download_state(eng, q_df, qb_df, qprime_df))) return rc;
-  return stats_after_step(eng);
+  rc = stats_after_step(eng);
+  const int rs = sample_after_step(eng);
+  return rc ? rc : rs;
 }
 
 int hnumo_set_resident(hnumo_engine *eng, int on) {
@@ -2032,6 +2055,277 @@ int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count
   return HNUMO_OK;
 }
 
+// ------------------------------------------------------------------ sample sets
+// (kernels_sample.hip, sample_plan.h; plain launches on the engine stream, outside the captured
+// step, like the statistics: the step's launches, graph and bits are the same with or without sets)
+static void sample_free(hnumo_engine *eng, int id) {
+  auto &s = eng->samples[id];
+  if (s.d_tab) (void)hipFree(s.d_tab);
+  for (double **p : {&s.d_w, &s.d_out, &s.d_series})
+    if (*p) (void)hipFree(*p);
+  s = hnumo_engine::SampleSet{};
+}
+
+static bool sample_ngl_ok(int ngl) { return ngl == 3 || ngl == 4 || ngl == 5 || ngl == 6 || ngl == 8; }
+
+// the set `id` of the engine, or nullptr with the message set
+static hnumo_engine::SampleSet *sample_set(hnumo_engine *eng, int32_t id, const char *who) {
+  if (id < 0 || id >= SP_MAXSETS || !eng->samples[id].used) {
+    fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no sample set with id " + std::to_string(id));
+    return nullptr;
+  }
+  return &eng->samples[id];
+}
+
+// the located or given points of `pl` become a set: tables built and uploaded
+static int sample_adopt(hnumo_engine *eng, SamplePlan &pl, const double *xgl, int32_t source, int32_t *id, const char *who) {
+  int slot = -1;
+  for (int i = 0; i < SP_MAXSETS && slot < 0; i++)
+    if (!eng->samples[i].used) slot = i;
+  if (slot < 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the engine holds " + std::to_string(SP_MAXSETS) +
+                                            " sample sets already (hnumo_sample_destroy frees one)");
+  const int V = sp_nval(eng->L, source);
+  sample_chunks(xgl, sp_K(eng->ngl, V), pl);
+  HIPCHK(hipSetDevice(eng->device));
+  auto &s = eng->samples[slot];
+  s = hnumo_engine::SampleSet{};
+  const size_t M = (size_t)pl.M, nch = (size_t)pl.nchunks(), nel = pl.el_list.size();
+  const size_t ntab = 2 * (nch + 1) + nel + 2 * M;
+  std::vector<int> tab;
+  tab.reserve(ntab);
+  for (const std::vector<int32_t> *v : {&pl.chunk_pt, &pl.chunk_el, &pl.el_list, &pl.slot, &pl.perm})
+    tab.insert(tab.end(), v->begin(), v->end());
+  bool ok = hipMalloc((void **)&s.d_tab, ntab * sizeof(int)) == hipSuccess &&
+            hipMalloc((void **)&s.d_w, pl.w.size() * sizeof(double)) == hipSuccess &&
+            hipMalloc((void **)&s.d_out, (size_t)V * M * sizeof(double)) == hipSuccess;
+  ok = ok && hipMemcpy(s.d_tab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(s.d_w, pl.w.data(), pl.w.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    sample_free(eng, slot);
+    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
+  }
+  s.d_chunk_pt = s.d_tab;
+  s.d_chunk_el = s.d_chunk_pt + nch + 1;
+  s.d_el_list = s.d_chunk_el + nch + 1;
+  s.d_slot = s.d_el_list + nel;
+  s.d_perm = s.d_slot + M;
+  s.source = source;
+  s.V = V;
+  s.plan = std::move(pl);
+  s.plan.w = std::vector<double>();   // (the device holds the weights and the work lists)
+  s.plan.slot = s.plan.perm = std::vector<int32_t>();
+  s.used = true;
+  *id = slot;
+  return HNUMO_OK;
+}
+
+static int sample_create_checks(hnumo_engine *eng, int32_t source, const int32_t *id, const char *who) {
+  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
+  if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE or HNUMO_SAMPLE_STATS, got " +
+                                            std::to_string(source));
+  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
+  return 0;
+}
+
+int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy, int64_t M,
+                        int32_t source, int32_t *id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create")) return rc;
+  SamplePlan pl;
+  if (int rc = sample_locate(coord, ldc, xgl, eng->ngl, eng->nelem_owned, xy, M, pl, eng->err)) return rc;
+  return sample_adopt(eng, pl, xgl, source, id, "hnumo_sample_create");
+}
+
+int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, const int32_t *elem, const double *xi_eta, int64_t M,
+                            int32_t source, int32_t *id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create_ref")) return rc;
+  SamplePlan pl;
+  if (int rc = sample_take_ref(xgl, eng->ngl, eng->nelem_owned, elem, xi_eta, M, pl, eng->err)) return rc;
+  return sample_adopt(eng, pl, xgl, source, id, "hnumo_sample_create_ref");
+}
+
+int hnumo_sample_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const auto *s = sample_set(eng, id, "hnumo_sample_plan");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->plan.M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_plan: M must be the set's " + std::to_string(s->plan.M) + ", got " +
+                                            std::to_string(M));
+  if (elem) std::memcpy(elem, s->plan.elem.data(), (size_t)M * sizeof(int32_t));
+  if (xi_eta) std::memcpy(xi_eta, s->plan.xi_eta.data(), 2 * (size_t)M * sizeof(double));
+  return HNUMO_OK;
+}
+
+extern "C++" template <int NGL, int SRC>
+static void sample_launch_L(hnumo_engine *eng, int nch, const SampleArgs &a) {
+  switch (eng->L) {
+    case 1: hipLaunchKernelGGL((sample_kernel<NGL, 1, SRC>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a); break;
+    case 2: hipLaunchKernelGGL((sample_kernel<NGL, 2, SRC>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a); break;
+    default: hipLaunchKernelGGL((sample_kernel<NGL, 3, SRC>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a); break;
+  }
+}
+
+extern "C++" template <int SRC>
+static void sample_launch_ngl(hnumo_engine *eng, int nch, const SampleArgs &a) {
+  switch (eng->ngl) {
+    case 3: sample_launch_L<3, SRC>(eng, nch, a); break;
+    case 4: sample_launch_L<4, SRC>(eng, nch, a); break;
+    case 5: sample_launch_L<5, SRC>(eng, nch, a); break;
+    case 6: sample_launch_L<6, SRC>(eng, nch, a); break;
+    default: sample_launch_L<8, SRC>(eng, nch, a); break;
+  }
+}
+
+// one sample of the set into `dst` [V][M] on the device, ordered after what is on the engine stream
+static int sample_now(hnumo_engine *eng, const hnumo_engine::SampleSet &s, double *dst, const char *who) {
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (s.source == HNUMO_SAMPLE_STATS) {
+    if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the flow statistics: call hnumo_stats_begin first");
+    if (eng->st_nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the flow statistics have no samples yet");
+  }
+  SampleArgs a{};
+  a.q = eng->q;
+  a.qb = eng->qb;
+  a.zbot = eng->nstat + (size_t)NS_ZB * eng->npoin;
+  a.alpha = eng->alpha;
+  a.sums = (const double2 *)eng->st_sums;
+  a.gravity = eng->p.gravity;
+  a.nsamp = (double)eng->st_nsamples;
+  a.chunk_pt = s.d_chunk_pt;
+  a.chunk_el = s.d_chunk_el;
+  a.el_list = s.d_el_list;
+  a.slot = s.d_slot;
+  a.perm = s.d_perm;
+  a.w = s.d_w;
+  a.out = dst;
+  a.npoin = (size_t)eng->npoin;
+  a.M = (size_t)s.plan.M;
+  if (s.source == HNUMO_SAMPLE_STATS)
+    sample_launch_ngl<SP_SRC_STATS>(eng, s.plan.nchunks(), a);
+  else
+    sample_launch_ngl<SP_SRC_STATE>(eng, s.plan.nchunks(), a);
+  HIPCHK(hipGetLastError());
+  return HNUMO_OK;
+}
+
+// planar [V][M] entries -> the caller's (V,M[,count])
+static void sample_transpose(const double *raw, int V, size_t M, size_t count, double *out) {
+  for (size_t c = 0; c < count; c++)
+    for (int v = 0; v < V; v++) {
+      const double *r = raw + (c * V + v) * M;
+      double *o = out + c * V * M + v;
+      for (size_t m = 0; m < M; m++) o[m * V] = r[m];
+    }
+}
+
+int hnumo_sample(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: out is NULL");
+  const int64_t want = (int64_t)s->V * s->plan.M;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: n must be V*M = " + std::to_string(want) + ", got " + std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  if (int rc = sample_now(eng, *s, s->d_out, "hnumo_sample")) return rc;
+  std::vector<double> raw((size_t)want);
+  HIPCHK(hipMemcpyAsync(raw.data(), s->d_out, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  sample_transpose(raw.data(), s->V, (size_t)s->plan.M, 1, out);
+  return HNUMO_OK;
+}
+
+int hnumo_sample_series_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample_series_begin");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (every < 0 || capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_series_begin: every and capacity must be >= 0, got " +
+                                            std::to_string(every) + ", " + std::to_string(capacity));
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a recording in flight writes the old series)
+  if (s->d_series) (void)hipFree(s->d_series);
+  s->d_series = nullptr;
+  s->every = s->cap = s->count = 0;
+  s->steps = 0;
+  if (capacity == 0) return HNUMO_OK;       // (no series: nothing to record into)
+  if (hipMalloc((void **)&s->d_series, (size_t)capacity * s->V * (size_t)s->plan.M * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    s->d_series = nullptr;
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_sample_series_begin: device allocation failed");
+  }
+  s->every = every;
+  s->cap = capacity;
+  return HNUMO_OK;
+}
+
+static int sample_record(hnumo_engine *eng, hnumo_engine::SampleSet &s, int id, const char *who) {
+  if (s.count >= s.cap)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series of sample set " + std::to_string(id) + " is full (" +
+                                            std::to_string(s.cap) + " samples): nothing recorded; read it with clear = 1");
+  if (int rc = sample_now(eng, s, s.d_series + (size_t)s.count * s.V * (size_t)s.plan.M, who)) return rc;
+  s.count++;
+  return HNUMO_OK;
+}
+
+static int sample_after_step(hnumo_engine *eng) {
+  int rc = 0;
+  for (int id = 0; id < SP_MAXSETS; id++) {
+    auto &s = eng->samples[id];
+    if (!s.used || s.every <= 0) continue;
+    if (++s.steps % s.every) continue;
+    const int r = sample_record(eng, s, id, "sample series after the step (the step itself succeeded)");
+    if (!rc) rc = r;
+  }
+  return rc;
+}
+
+int hnumo_sample_record(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample_record");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return sample_record(eng, *s, id, "hnumo_sample_record");
+}
+
+int hnumo_sample_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample_series");
+  if (!s) return HNUMO_ERR_INVALID;
+  const int64_t want = (int64_t)s->V * s->plan.M * s->count;
+  if (n < 0 || (out && n < want))
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_series: out holds n = " + std::to_string(n) +
+                                            " values, the series has V*M*count = " + std::to_string(want));
+  HIPCHK(hipSetDevice(eng->device));
+  if (out && want > 0) {
+    std::vector<double> raw((size_t)want);
+    HIPCHK(hipMemcpyAsync(raw.data(), s->d_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    HIPCHK(hipStreamSynchronize(eng->stream));
+    HIPCHK(hipGetLastError());
+    sample_transpose(raw.data(), s->V, (size_t)s->plan.M, (size_t)s->count, out);
+  }
+  if (count) *count = s->count;
+  // (the next recording's slot is written after this copy on the same stream)
+  if (clear && out) s->count = 0;
+  return HNUMO_OK;
+}
+
+int hnumo_sample_destroy(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!sample_set(eng, id, "hnumo_sample_destroy")) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the set's tables)
+  sample_free(eng, id);
+  return HNUMO_OK;
+}
+
 int hnumo_btp_bcl_coeffs(hnumo_engine *eng, const double *qprime_df) {
   if (!eng) return HNUMO_ERR_INVALID;
   int rc = component_transport_check(eng);
@@ -2409,6 +2703,7 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
   for (int i = 0; i < n; i++) {
     (void)hipSetDevice(engines[i]->device);
     if (int r = stats_after_step(engines[i])) return r;
+    if (int r = sample_after_step(engines[i])) return r;
   }
   return 0;
 }

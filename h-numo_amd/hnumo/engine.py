@@ -76,6 +76,15 @@ def lib():
         L.hnumo_stats_fields.argtypes = [vp, dp, C.c_int64]
         L.hnumo_stats_series.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]
         L.hnumo_stats_end.argtypes = [vp]
+        ip, i32, i64 = C.POINTER(C.c_int32), C.c_int32, C.c_int64
+        L.hnumo_sample_create.argtypes = [vp, dp, i32, dp, dp, i64, i32, ip]
+        L.hnumo_sample_create_ref.argtypes = [vp, dp, ip, dp, i64, i32, ip]
+        L.hnumo_sample_plan.argtypes = [vp, i32, ip, dp, i64]
+        L.hnumo_sample.argtypes = [vp, i32, dp, i64]
+        L.hnumo_sample_series_begin.argtypes = [vp, i32, i32, i32]
+        L.hnumo_sample_record.argtypes = [vp, i32]
+        L.hnumo_sample_series.argtypes = [vp, i32, dp, i64, C.POINTER(i64), i32]
+        L.hnumo_sample_destroy.argtypes = [vp, i32]
         _lib = L
     return _lib
 
@@ -94,6 +103,7 @@ def _dp(a, size=None, name="array"):
 
 SUMMATION = {"reference": 0, "factored": 1}   # HNUMO_SUM_REFERENCE / HNUMO_SUM_FACTORED
 DIAG_MASS = 1                                 # HNUMO_DIAG_MASS
+SAMPLE_STATE, SAMPLE_STATS = 0, 1             # HNUMO_SAMPLE_STATE / HNUMO_SAMPLE_STATS
 
 
 def unpack_diagnostics(out, L: int) -> dict:
@@ -320,6 +330,98 @@ class Engine:
 
     def stats_end(self):
         self._check(lib().hnumo_stats_end(self.h))
+
+    # ---- sample sets on the device state (hnumo_sample_*; mirror and helpers: hnumo/sample.py)
+    def _sample_nval(self, source: int) -> int:
+        L = self.dims["nlayers"]
+        return 5 * L if source == SAMPLE_STATS else 5 * L + 4
+
+    def sample_create(self, coord, xgl, xy, source: int = 0) -> int:
+        """A set from physical points xy (2, M), located in the owned elements from coord
+        (2 or 3, npoin) and the LGL nodes xgl; source: SAMPLE_STATE or SAMPLE_STATS.  Returns its id."""
+        coord = np.asfortranarray(coord, dtype=np.float64)
+        if coord.ndim != 2 or coord.shape[1] != self.dims["npoin"]:
+            raise ValueError(f"coord: shape {coord.shape}, expected (2 or 3, {self.dims['npoin']})")
+        xgl = self._sample_xgl(xgl)
+        xy = np.asfortranarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[0] != 2:
+            raise ValueError(f"xy: shape {xy.shape}, expected (2, M)")
+        sid = C.c_int32(-1)
+        dp = C.POINTER(C.c_double)
+        self._check(lib().hnumo_sample_create(self.h, coord.ctypes.data_as(dp), coord.shape[0], xgl.ctypes.data_as(dp),
+                                              xy.ctypes.data_as(dp), xy.shape[1], int(source), C.byref(sid)))
+        self._sample_sets[sid.value] = (xy.shape[1], self._sample_nval(source))
+        return sid.value
+
+    def sample_create_ref(self, xgl, elem, xi_eta, source: int = 0) -> int:
+        """A set from given locations: elem (M) 1-based local elements (0: not on this rank) and
+        xi_eta (2, M) in [-1,1].  Returns its id."""
+        xgl = self._sample_xgl(xgl)
+        elem = np.ascontiguousarray(elem, dtype=np.int32).reshape(-1)
+        xe = np.asfortranarray(xi_eta, dtype=np.float64)
+        if xe.ndim != 2 or xe.shape != (2, elem.size):
+            raise ValueError(f"xi_eta: shape {xe.shape}, expected (2, {elem.size})")
+        sid = C.c_int32(-1)
+        dp = C.POINTER(C.c_double)
+        self._check(lib().hnumo_sample_create_ref(self.h, xgl.ctypes.data_as(dp), elem.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  xe.ctypes.data_as(dp), elem.size, int(source), C.byref(sid)))
+        self._sample_sets[sid.value] = (elem.size, self._sample_nval(source))
+        return sid.value
+
+    def _sample_xgl(self, xgl):
+        xgl = np.ascontiguousarray(xgl, dtype=np.float64).reshape(-1)
+        if xgl.size != self.dims["ngl"]:
+            raise ValueError(f"xgl: {xgl.size} nodes, expected ngl = {self.dims['ngl']}")
+        return xgl
+
+    @property
+    def _sample_sets(self) -> dict:
+        """id -> (M, V) of the sets created through this object (the sizes of their read-outs)."""
+        return self.__dict__.setdefault("_sample_sets_", {})
+
+    def _sample_shape(self, sid: int):
+        if sid not in self._sample_sets:
+            raise EngineError(4, f"no sample set with id {sid}")
+        return self._sample_sets[sid]
+
+    def sample_plan(self, sid: int):
+        """(elem (M) int32, xi_eta (2, M)) of the set."""
+        M, _ = self._sample_shape(sid)
+        elem = np.zeros(M, dtype=np.int32)
+        xe = np.zeros((2, M), order="F")
+        self._check(lib().hnumo_sample_plan(self.h, int(sid), elem.ctypes.data_as(C.POINTER(C.c_int32)), _dp(xe), M))
+        return elem, xe
+
+    def sample(self, sid: int):
+        """(V, M): the set sampled on the device now (no sync)."""
+        M, V = self._sample_shape(sid)
+        out = np.zeros((V, M), order="F")
+        self._check(lib().hnumo_sample(self.h, int(sid), _dp(out), out.size))
+        return out
+
+    def sample_series_begin(self, sid: int, every: int = 0, capacity: int = 0):
+        """(Re)allocate the set's series of `capacity` samples on the device.  every = k >= 1: the
+        engine records after every k-th successful step; every = 0: sample_record() does."""
+        self._check(lib().hnumo_sample_series_begin(self.h, int(sid), int(every), int(capacity)))
+
+    def sample_record(self, sid: int):
+        """Append one sample to the set's series on the device; nothing is copied back."""
+        self._check(lib().hnumo_sample_record(self.h, int(sid)))
+
+    def sample_series(self, sid: int, clear: bool = False):
+        """(V, M, count): the recorded samples; clear empties the series afterwards."""
+        M, V = self._sample_shape(sid)
+        n = C.c_int64()
+        self._check(lib().hnumo_sample_series(self.h, int(sid), None, 0, C.byref(n), 0))
+        out = np.zeros((V, M, n.value), order="F")
+        if n.value or clear:
+            buf = out if out.size else np.zeros(1)
+            self._check(lib().hnumo_sample_series(self.h, int(sid), _dp(buf), out.size, C.byref(n), int(clear)))
+        return out
+
+    def sample_destroy(self, sid: int):
+        self._check(lib().hnumo_sample_destroy(self.h, int(sid)))
+        self._sample_sets.pop(sid, None)
 
     def bench_steps(self, nsteps: int):
         t = C.c_double()

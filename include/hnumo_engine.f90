@@ -85,8 +85,11 @@ module hnumo_engine_c
         hnumo_set_summation, hnumo_get_summation, hnumo_stage_path, hnumo_persistent_info, hnumo_predict, &
         hnumo_rccl_unique_id, hnumo_persistent_stats, hnumo_diag_geometry, hnumo_diagnostics, &
         hnumo_layer_fields, hnumo_stats_begin, hnumo_stats_accumulate, hnumo_stats_sums, &
-        hnumo_stats_set_sums, hnumo_stats_fields, hnumo_stats_series, hnumo_stats_end
+        hnumo_stats_set_sums, hnumo_stats_fields, hnumo_stats_series, hnumo_stats_end, &
+        hnumo_sample_create, hnumo_sample_create_ref, hnumo_sample_plan, hnumo_sample, &
+        hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
+    integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1   ! sample set sources
 
     interface
         integer(c_int) function hnumo_engine_create(mesh, statics, params, halo, device, eng) &
@@ -295,6 +298,80 @@ module hnumo_engine_c
             import :: c_int, c_ptr
             type(c_ptr), value :: eng
         end function hnumo_stats_end
+
+        ! Sample sets (see include/hnumo_engine.h): the device state, or the flow statistics, at
+        ! arbitrary points by the element's own Lagrange interpolant -- an output grid, a
+        ! cross-section, stations -- on demand or after every k-th step into a series on the device.
+        ! coord(ldc,npoin) and xgl(ngl) are mod_grid's coord and mod_basis' xgl; xy(2,M) the points.
+        integer(c_int) function hnumo_sample_create(eng, coord, ldc, xgl, xy, M, source, id) &
+                bind(C, name='hnumo_sample_create')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: coord(*), xgl(*), xy(*)
+            integer(c_int32_t), value :: ldc, source
+            integer(c_int64_t), value :: M
+            integer(c_int32_t), intent(out) :: id
+        end function hnumo_sample_create
+
+        ! elem(M): 1-based local element, 0 = not on this rank; xi_eta(2,M) in [-1,1]
+        integer(c_int) function hnumo_sample_create_ref(eng, xgl, elem, xi_eta, M, source, id) &
+                bind(C, name='hnumo_sample_create_ref')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: xgl(*), xi_eta(*)
+            integer(c_int32_t), intent(in) :: elem(*)
+            integer(c_int64_t), value :: M
+            integer(c_int32_t), value :: source
+            integer(c_int32_t), intent(out) :: id
+        end function hnumo_sample_create_ref
+
+        integer(c_int) function hnumo_sample_plan(eng, id, elem, xi_eta, M) bind(C, name='hnumo_sample_plan')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            integer(c_int32_t), intent(out) :: elem(*)
+            real(c_double), intent(out) :: xi_eta(*)
+            integer(c_int64_t), value :: M
+        end function hnumo_sample_plan
+
+        ! out(V,M), n = V*M; V = 5*nlayers + 4 (HNUMO_SAMPLE_STATE) or 5*nlayers (HNUMO_SAMPLE_STATS)
+        integer(c_int) function hnumo_sample(eng, id, out, n) bind(C, name='hnumo_sample')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_sample
+
+        integer(c_int) function hnumo_sample_series_begin(eng, id, every, capacity) &
+                bind(C, name='hnumo_sample_series_begin')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id, every, capacity
+        end function hnumo_sample_series_begin
+
+        integer(c_int) function hnumo_sample_record(eng, id) bind(C, name='hnumo_sample_record')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+        end function hnumo_sample_record
+
+        ! out(V,M,count); n = size(out) >= V*M*count; clear = 1 empties the series after the copy
+        integer(c_int) function hnumo_sample_series(eng, id, out, n, count, clear) bind(C, name='hnumo_sample_series')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: count
+            integer(c_int32_t), value :: clear
+        end function hnumo_sample_series
+
+        integer(c_int) function hnumo_sample_destroy(eng, id) bind(C, name='hnumo_sample_destroy')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+        end function hnumo_sample_destroy
     end interface
 
 contains

@@ -299,6 +299,65 @@ int hnumo_stats_fields(hnumo_engine *eng, double *out, int64_t n);
 int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear);
 int hnumo_stats_end(hnumo_engine *eng);
 
+/* Sample sets (additive in ABI v10): the state on the device, or the accumulated flow statistics,
+ * evaluated at arbitrary points -- a regular output grid, a cross-section, a few stations -- by the
+ * element's own Lagrange interpolant, where the post-processing scripts griddata the synced nodal
+ * values (Examples/double_gyre/compute_ssh.m:58-70, compute_ke.m, plot_gyre.m, Examples/bump/
+ * plot_bump*.m, Examples/lake/plot_lake_2D.m).  On demand, or after every k-th step into a series
+ * kept on the device: a station series from every step without one hnumo_sync.  DESIGN.md §6.1.2.
+ *
+ * A set is M points, each a 1-based local element (0: not on this rank) and reference coordinates
+ * (xi, eta) in [-1,1]^2, with the 1-D LGL nodes xgl(ngl) (mod_basis xgl).  Weights, once per set on
+ * the host: Lx[i] = l_i(xi) by w = 1; for m = 0..ngl-1, m != i: w = w * ((xi - xgl[m]) / (xgl[i] -
+ * xgl[m])) (each factor a quotient first, multiplied in the order of m); Ly[j] from eta likewise.
+ * Nodal fields of the element, node I = e*P + j*ngl + i:
+ *   HNUMO_SAMPLE_STATE  V = 5*nlayers + 4 values per point: rows 5(k-1)+1..5k = layer k's h, u, v,
+ *                       dp, elevation exactly as hnumo_layer_fields forms them, then qb_df(1:4, I)
+ *   HNUMO_SAMPLE_STATS  V = 5*nlayers: hbar, um, vm, mke, eke of hnumo_stats_fields per layer
+ * Value: val = sum_j Ly[j] * r_j with r_j = sum_i Lx[i] * F(e, j*ngl + i), both sums left to right
+ * from their first product (no FMA).  Points with elem = 0 read 0.0 in every row.  At xi = xgl[a],
+ * eta = xgl[b] the weights are exactly 0 and 1: the sample is the nodal value.  Every value has the
+ * bits of the numpy mirror hnumo/sample.py (HostSampler) on the synced state.
+ *
+ * hnumo_sample_create: locates xy(2,M) in the rank's OWNED elements from coord(ldc,npoin) (ldc = 2
+ *   or 3, as hnumo_diag_geometry takes it).  Elements are straight-sided bilinear quadrilaterals
+ *   (every node the bilinear map of the four corner nodes at (xgl(i), xgl(j)) to within 64 eps
+ *   max|coord|: a curved element is an error).  The map is inverted with Newton; an element accepts
+ *   a point when max(|xi|, |eta|) <= 1 + tol_e, tol_e = 64 eps max|coord| / (half the element's
+ *   shortest edge); the lowest accepting element wins and (xi, eta) are clamped to [-1,1].  A point
+ *   no element accepts (outside the rank's owned elements, or not finite) gets elem = 0.
+ * hnumo_sample_create_ref: takes elem(M) in 0..nelem_owned and xi_eta(2,M) in [-1,1] as given.
+ *   Both return the set's id (0..7: up to 8 sets per engine; hnumo_engine_destroy frees them).
+ * hnumo_sample_plan: the set's elem(M) and xi_eta(2,M) (either may be NULL); M must be the set's.
+ * hnumo_sample: samples now and copies out(V,M), n = V*M.
+ * hnumo_sample_series_begin: (re)allocates the set's series of `capacity` samples on the device and
+ *   empties it (capacity = 0: no series).  every = 0: only hnumo_sample_record appends; every =
+ *   k >= 1: the engine also appends after every k-th successful hnumo_ti_rk_bcl (hnumo_group_ti_rk_bcl
+ *   for grouped engines) since begin, once the step's abort / retry handling has finished and after
+ *   the flow statistics' own sample of that step (a STATS set sees the new sums).  If the series is
+ *   full then, the step call returns 4 (the step is done).
+ * hnumo_sample_record: appends one sample to the series on the device; nothing is copied back.
+ * hnumo_sample_series: out(V,M,count); n = the doubles out can hold, at least V*M*count; out = NULL
+ *   (n = 0) only returns count.  clear = 1 empties the series after the copy.
+ * hnumo_sample_destroy: frees the set; its id is given out again.
+ * All launches are plain launches on the engine stream outside the captured step: the step's
+ * launches, graph and bits are the same with or without sets.  All return 4, with a message in
+ * hnumo_last_error, for an unknown id, a wrong n or M, negative arguments, invalid points or
+ * geometry, a ninth set; a sample returns 4 before any state was uploaded, when the series is full
+ * or absent, and for a STATS set before hnumo_stats_begin or with no statistics samples.        */
+#define HNUMO_SAMPLE_STATE 0
+#define HNUMO_SAMPLE_STATS 1
+int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
+                        int64_t M, int32_t source, int32_t *id);
+int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, const int32_t *elem, const double *xi_eta, int64_t M,
+                            int32_t source, int32_t *id);
+int hnumo_sample_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M);
+int hnumo_sample(hnumo_engine *eng, int32_t id, double *out, int64_t n);
+int hnumo_sample_series_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t capacity);
+int hnumo_sample_record(hnumo_engine *eng, int32_t id);
+int hnumo_sample_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear);
+int hnumo_sample_destroy(hnumo_engine *eng, int32_t id);
+
 /* Summation order of the barotropic stage (no reference counterpart: the reference has
  * one order).  HNUMO_SUM_REFERENCE (the default) evaluates the volume integral and the
  * nodal -> quad interpolation as the reference's dense psih/dpsidx sums in its order:
