@@ -349,8 +349,11 @@ struct Launch {
     e->occ_blocks[1] = nb1;
     e->occ_ncu = ncu;
     const bool est = e->persist_guard & 1;
-    e->persistent_ok[0] = !est || (long)nb0 * ncu >= e->nelem_owned;
-    e->persistent_ok[1] = !est || (long)nb1 * ncu >= e->nelem_owned;
+    // the kernel packs a trace slot index into 18 bits (stage_body, GD_SLOT): any grid that can be
+    // resident is far below that (3 workgroups on each of 256 CUs: 768 x 32 NGL slots)
+    const bool persist_slots_ok = (long)e->nelem * 32 * NGL <= (1L << 18);
+    e->persistent_ok[0] = persist_slots_ok && (!est || (long)nb0 * ncu >= e->nelem_owned);
+    e->persistent_ok[1] = persist_slots_ok && (!est || (long)nb1 * ncu >= e->nelem_owned);
     e->regacc[0] = StageCfg<NGL, NQ, false>::REGACC;
     e->regacc[1] = StageCfg<NGL, NQ, true>::REGACC;
   }

@@ -447,7 +447,7 @@ __device__ __forceinline__ void wall_ghost(int er, const double *efn, int n, dou
 template <int NGL, int NQ, bool SF, bool PERSIST, class ARGS, int NB = 0, int ACCF = 0, int FST = 0>
 __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsigned long long *s_prof,
                                            const int e, const int tid, unsigned long long ep = 0,
-                                           double *pacc = nullptr) {
+                                           double *pacc = nullptr, int *gdesc = nullptr) {
   static_assert(PERSIST ? (FST == 1 || FST == 2) : FST == 0, "FST is the persistent stage position");
   const int accm = ACCF == 1 ? 2 : (ACCF == 2 ? 1 : a.accumulate);
   constexpr bool first = FST != 2;
@@ -528,6 +528,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   __builtin_amdgcn_s_setprio(PRIO_B);
   // (persistent, later stages: zeroed behind the previous stage's clocks, see the end of the body)
   if (PROF && tid == 0 && (!PERSIST || first)) s_prof[22] = 0;
+  if (PROF && tid == 0 && PERSIST && !C::SLIM && first) s_prof[28] = 0;
   const bool use_q0 = !a.rhs_only && a.a1 != 0.0, use_q2 = !a.rhs_only && a.a3 != 0.0;
   const int qpm = (SF || !m.botfr || !a.qpq) ? 0 : a.qpq_mode;  // see StageArgs::qpq
   if (!DBG(4096)) {
@@ -643,19 +644,63 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   static_assert(32 * NGL <= BS, "at most one granule per thread (issue_granule, poll_traces)");
   granule_u4 gx = {0u, 0u, 0u, 0u};
   bool gwant = false;
+  // persistent, non-slim arenas: thread t < 32 NGL hands over granule t = (face lf, component c, node n)
+  // in both directions -- it stores its own trace value into the neighbour's slot (E2, and stage 0's
+  // self_trace scatter) and receives the neighbour's value in slot t of this element.  Which face,
+  // which LDS word and which slot does not change over a launch: the first stage packs them into one
+  // register that the stage loop carries, GD_SRC bits of arena word index below GD_SLOT bits of
+  // out-slot index, or -1 where the face has no neighbour.  (A single rank has no processor faces, and
+  // only a single rank runs this path: bc == 0 does not occur, so one validity serves both directions.)
+  constexpr bool GDESC = PERSIST && !C::SLIM && NGL <= 6;  // (N = 7, either summation: as before)
+  constexpr int GD_SRC = 13, GD_SLOT = 18;
+  int gd = -1;
+  if constexpr (GDESC) {
+    static_assert(INPL, "the trace source of the new state is s_qb");
+    static_assert(C::ARENA <= (1 << GD_SRC), "arena word index in GD_SRC bits");
+    static_assert(GD_SRC + GD_SLOT == 31, "the sign bit marks a face without neighbour");
+    if constexpr (first) {
+      if (tid < 32 * NGL) {
+        const int lf = tid / (8 * NGL), c = (tid / NGL) % 8, n = tid % NGL;
+        if (s_bc[lf] > 0) {  // interior face (the engine bounds nelem * 32 NGL by 2^GD_SLOT: persist_slots_ok)
+          const int p = s_map[lf * NGL + n];
+          const int src = c < 4 ? C::O_QB + p * 4 + c : C::O_GR + (c - 4) * P + p;
+          const int slot = ((s_nbe[lf] * 4 + s_nblf[lf]) * 8 + c) * NGL + n;
+          gd = (slot << GD_SRC) | src;
+        }
+      }
+      *gdesc = gd;
+    } else {
+      gd = *gdesc;
+    }
+  }
+  // this thread's trace granule into the neighbour's slot of buffer base: one LDS read and one 16-byte
+  // write-through (sc1) buffer store, untorn like st_granule's
+  auto put_granule = [&](TraceGranule *base, unsigned long long tag) {
+    if constexpr (GDESC) {
+      if (gd >= 0) {
+        const unsigned long long vb = __builtin_bit_cast(unsigned long long, S[gd & ((1 << GD_SRC) - 1)]);
+        const granule_u4 x = {(unsigned)vb, (unsigned)(vb >> 32), (unsigned)tag, (unsigned)(tag >> 32)};
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)base, 0, m.nelem * 32 * NGL * (int)sizeof(TraceGranule), 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b128(x, r, (gd >> GD_SRC) * (int)sizeof(TraceGranule), 0, 16 /* sc1 */);
+      }
+    }
+  };
   // issue this thread's granule load now; poll_traces checks it and polls again while
   // it is older than this stage
   auto issue_granule = [&]() {
     if constexpr (PERSIST) {
-      if (tid < 32 * NGL) {
-        gwant = s_bc[tid / (8 * NGL)] > 0;  // interior face: a neighbour writes this slot
-        if (gwant) {
-          // a compiler-tracked sc1 (L1-bypassing, L2-served) 16-byte load: it may stay in
-          // flight across phases, and the compiler waits for it where gx is first used
-          const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-              (void *)(a.gtr_in + (size_t)e * 32 * NGL), 0, 32 * NGL * (int)sizeof(TraceGranule), 0x00020000);
-          gx = __builtin_amdgcn_raw_buffer_load_b128(r, tid * (int)sizeof(TraceGranule), 0, 16 /* sc1 */);
-        }
+      // interior face: a neighbour writes this slot
+      if constexpr (GDESC)
+        gwant = gd >= 0;
+      else
+        gwant = tid < 32 * NGL && s_bc[tid / (8 * NGL)] > 0;
+      if (gwant) {
+        // a compiler-tracked sc1 (L1-bypassing, L2-served) 16-byte load: it may stay in
+        // flight across phases, and the compiler waits for it where gx is first used
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)(a.gtr_in + (size_t)e * 32 * NGL), 0, 32 * NGL * (int)sizeof(TraceGranule), 0x00020000);
+        gx = __builtin_amdgcn_raw_buffer_load_b128(r, tid * (int)sizeof(TraceGranule), 0, 16 /* sc1 */);
       }
     }
   };
@@ -670,6 +715,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
         double v = __builtin_bit_cast(double, ((unsigned long long)gx[1] << 32) | gx[0]);
         unsigned long long tag = ((unsigned long long)gx[3] << 32) | gx[2];
         unsigned spins = 0;
+        if (PROF && tag != want) s_prof[28] = 1;  // this stage re-polls (counted at the end of the body)
         while (tag != want && !DBG(16)) {
           __builtin_amdgcn_s_sleep(1);
           ld_granule(g, v, tag);
@@ -905,8 +951,10 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
         for (int c = 0; c < 4; c++) s_grad[c * P + p] = g[c];
       }
       LDS_BARRIER();
-      // (E2's scatter from the input state, a copy: shared, it measured slower -- the figures are at sum_last_v)
-      for (int t = tid; t < 4 * 8 * NGL; t += BS) {
+      // (E2's scatter from the input state: with the same descriptor, s_qb holds the input here;
+      // otherwise a copy of E2's loop: shared, it measured slower -- the figures are at sum_last_v)
+      if constexpr (GDESC) put_granule(a.gtr_in, (ep << 20) | a.tag_in);
+      else for (int t = tid; t < 4 * 8 * NGL; t += BS) {
         const int lf = t / (8 * NGL), c = (t / NGL) % 8, n = t % NGL;
         if (s_bc[lf] < 0) continue;
         const int p = s_map[lf * NGL + n];
@@ -1845,7 +1893,9 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   if (a.write_trace && !DBG(2048)) {
     // traces of the new state on each interior face, into the neighbour's slot:
     // qb(4) and grad(u_bar)(4) at the face nodes
-    for (int t = tid; t < 4 * 8 * NGL; t += BS) {
+    // (persistent, non-slim: from this thread's launch-invariant descriptor, see put_granule)
+    if constexpr (GDESC) put_granule(a.gtr_out, (ep << 20) | a.tag_out);
+    else for (int t = tid; t < 4 * 8 * NGL; t += BS) {
       asm volatile("" ::: "memory");
       const int lf = t / (8 * NGL), c = (t / NGL) % 8, n = t % NGL;
       if (s_bc[lf] < 0) continue;  // (processor faces: into the face's send slot)
@@ -1889,12 +1939,18 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     if (tid == 0) {
       if (PERSIST) {  // sums over the stages: A incl. the trace waits | the rest | stages
         if (first) s_prof[24] = s_prof[25] = s_prof[26] = s_prof[27] = s_prof[8] = s_prof[9] = s_prof[10] = s_prof[11] = s_prof[29] = 0;
+        // (non-slim arenas, whose slots 23 and 28 are otherwise unused: the stages in which a thread
+        // of this block found an old tag in its early granule load and polled again)
+        if (!C::SLIM) s_prof[23] = first ? s_prof[28] : s_prof[23] + s_prof[28];
         // per-phase sums over the stages: A2 | B | D | E, and (SLIM) the volume sums of wave 0
         s_prof[8] += s_prof[1] - s_prof[21];
         s_prof[9] += s_prof[2] - s_prof[1];
         s_prof[10] += s_prof[3] - s_prof[2];
         s_prof[11] += s_prof[5] - s_prof[3];
-        if (C::SLIM) s_prof[29] += s_prof[28] - s_prof[2];
+        if (C::SLIM)
+          s_prof[29] += s_prof[28] - s_prof[2];
+        else
+          s_prof[29] += s_prof[5] - s_prof[4];  // (non-slim: E2, the trace stores)
         s_prof[27] += s_prof[22];
         s_prof[24] += s_prof[21] - s_prof[0];
         s_prof[25] += s_prof[5] - s_prof[21];
@@ -1903,6 +1959,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       s_prof[31] = wall_clock64();
       for (int k = 0; k < 32; k++) a.prof[(size_t)e * 32 + k] = s_prof[k];
       if (PERSIST) s_prof[22] = 0;  // the next stage's longest trace wait (the stage loop's barrier follows)
+      if (PERSIST && !C::SLIM) s_prof[28] = 0;
     }
   }
 }
@@ -1998,6 +2055,7 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
   double pacc[16];  // this thread's time averages (StageCfg::REGACC)
 #pragma unroll
   for (int k = 0; k < 16; k++) pacc[k] = 0.0;
+  int gdesc = -1;  // this thread's trace-granule descriptor, formed by the first stage (stage_body, put_granule)
   // the first stage peeled off the stage loop, so that neither copy of the body branches on it (two
   // inlined bodies; C3 35.8 -> 34.8-35.4 us per stage, dg25L3 unchanged, same bits:
   // profiles/r06/ab_pfirst.log)
@@ -2005,7 +2063,7 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
     int tid_s = tid, e_s = e;
     asm volatile("" : "+v"(tid_s), "+s"(e_s));
     tid_s &= C::BS - 1;
-    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 1>(tab[0], s_arena, s_prof, e_s, tid_s, ep, pacc);
+    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 1>(tab[0], s_arena, s_prof, e_s, tid_s, ep, pacc, &gdesc);
   }
 #pragma unroll 1
   for (int stage = 1; stage < NS; stage++) {
@@ -2022,7 +2080,7 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
     int tid_s = tid, e_s = e;
     asm volatile("" : "+v"(tid_s), "+s"(e_s));
     tid_s &= C::BS - 1;  // restore the known range of the thread index
-    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 2>(tab[stage], s_arena, s_prof, e_s, tid_s, ep, pacc);
+    stage_body<NGL, NQ, SF, true, CStageArgs, 0, 0, 2>(tab[stage], s_arena, s_prof, e_s, tid_s, ep, pacc, &gdesc);
   }
   // the next launch's tags: every workgroup read the epoch at its start, so the last one to
   // finish (agent-scope counter) moves it on and resets the counters (every workgroup has passed

@@ -1,7 +1,9 @@
 """Stage-kernel time under HNUMO_STAGE_DBG phase switches (timing only: the switches break the
 physics), one case build, one engine per setting.  GPU only; diagnostics.
 Usage: python tools/dbg_sweep.py <cfg> <dbg> [<dbg> ...]   (bits: 1 no face projections,
-2 no Laplacian, 4 no volume sums, 32 no time averages)"""
+2 no Laplacian, 4 no volume sums, 32 no time averages; persistent: 16 no trace re-polls, 2048 no
+E2 trace stores -- only together with 16 (2064): without the stores every poll runs into its
+spin limit)"""
 import os
 import sys
 

@@ -75,12 +75,16 @@ if getattr(eng, "stage_path", "") == "persistent" and (pr[:, 26] > 0).all():
     bpc = c[np.searchsorted(u, key)]
     print(f"  persistent: per stage A(+waits) mean {aw.mean():.0f} clk, work mean {wk.mean():.0f} clk")
     ph = [pr[:, k] / nst for k in (8, 9, 10, 11, 29)]
-    print("  persistent per-stage phase means: A2 %.0f | B %.0f | D %.0f (wave-0 volume sums %.0f) | E %.0f clk"
-          % (ph[0].mean(), ph[1].mean(), ph[2].mean(), ph[4].mean(), ph[3].mean()))
+    slim = eng.dims["ngl"] >= 8  # (the slim N=7 arena: slot 29 is wave 0's volume sums, slots 23/28 the last D split)
+    print("  persistent per-stage phase means: A2 %.0f | B %.0f | D %.0f (%s %.0f) | E %.0f clk"
+          % (ph[0].mean(), ph[1].mean(), ph[2].mean(), "wave-0 volume sums" if slim else "of E: E2 trace stores",
+             ph[4].mean(), ph[3].mean()))
+    rp = None if slim else pr[:, 23] / nst  # share of the stages in which the block polled again
     if (pr[:, 23] > 0).all() and (pr[:, 28] > 0).all():  # SLATE (N=7): the last stage's D split
         print("  last stage, from D's start: volume sums done %.0f clk, the last wave's D work done %.0f clk"
               % ((pr[:, 28] - pr[:, 2]).mean(), (pr[:, 23] - pr[:, 2]).mean()))
     for k in sorted(set(bpc.tolist())):
         sel = bpc == k
         print(f"    CUs with {k} blocks: {sel.sum()} blocks, A(+waits) {aw[sel].mean():.0f}, work {wk[sel].mean():.0f} "
-              f"(max {wk[sel].max():.0f}) clk, trace wait {wt[sel].mean():.0f}, work-wait {(wk - wt)[sel].mean():.0f}")
+              f"(max {wk[sel].max():.0f}) clk, trace wait {wt[sel].mean():.0f}, work-wait {(wk - wt)[sel].mean():.0f}"
+              + ("" if slim else f", E2 {ph[4][sel].mean():.0f}, stages with a re-poll {100 * rp[sel].mean():.1f} %"))
