@@ -5,8 +5,9 @@
 // baroclinic step (2 barotropic sub-cycles = 2*N_btp*kstages fused stage kernels plus
 // ~20 baroclinic kernels) is captured once into a hipGraph and replayed.  The run diagnostics of
 // the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) and the
-// online flow statistics (kernels_stats.hip: hnumo_stats_*) are plain launches on the same stream
-// between replays.
+// online flow statistics (kernels_stats.hip: hnumo_stats_*), the sample sets (kernels_sample.hip) and
+// the float sets (kernels_float.hip: hnumo_floats_*) are plain launches on the same stream between
+// replays.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -26,12 +27,14 @@
 #include "engine_internal.h"
 #include "setup_plan.h"
 #include "sample_plan.h"
+#include "float_plan.h"
 #include "kernels_bcl.hip"
 #include "kernels_btp.hip"
 #include "kernels_lapq.hip"
 #include "kernels_diag.hip"
 #include "kernels_stats.hip"
 #include "kernels_sample.hip"
+#include "kernels_float.hip"
 
 using namespace hnumo;
 
@@ -210,6 +213,27 @@ struct hnumo_engine {
     int every = 0, cap = 0, count = 0;
     int64_t steps = 0;
   } samples[SP_MAXSETS];
+  // float sets (kernels_float.hip; hnumo_floats_*): the side neighbours of the owned elements, derived
+  // once at create from face / imapl / imapr (fl_nbr_err: why not, reported by hnumo_floats_create);
+  // per set the host geometry (float_plan.h; hnumo_floats_set locates in it), the permutation back to
+  // input order, the element tables and the SoA floats on the device, the series [capacity][5][M];
+  // advances since hnumo_floats_begin (a record after every record_every-th)
+  std::vector<int32_t> fl_nbr;
+  std::string fl_nbr_err;
+  bool fl_rows = false;                    // one lane per float; HNUMO_FLOAT_ROWS=1: a row per lane (the mapping not kept)
+  struct FloatSet {
+    bool used = false;
+    int64_t M = 0;
+    FloatGeom geom;
+    std::vector<int32_t> perm;
+    double *d_geo = nullptr;               // corners [E][8] | tol [E]
+    int *d_nbr = nullptr;                  // [E][4]
+    double *d_f = nullptr;                 // x | y | wx | wy | xi | eta, [M] each
+    int *d_i = nullptr;                    // elem | layer | status | fresh | perm, [M] each
+    double *d_series = nullptr;
+    int every = 0, rec_every = 0, cap = 0, count = 0;
+    int64_t advances = 0;
+  } floats[FL_MAXSETS];
 };
 
 // the per-kernel breakdown's mark after a launch on the engine stream (no-op outside
@@ -1073,6 +1097,8 @@ static void adopt_plan(hnumo_engine *eng, const hnumo_mesh_desc *mesh, const hnu
   }
   eng->ssprk_a.assign(st->ssprk_a, st->ssprk_a + 3 * par->kstages);
   eng->ssprk_beta.assign(st->ssprk_beta, st->ssprk_beta + par->kstages);
+  if (float_side_neighbours(mesh->face, mesh->imapl, mesh->imapr, F, ngl, E, pl.nelem_owned, eng->fl_nbr, eng->fl_nbr_err))
+    eng->fl_nbr.clear();                   // (no float sets on this mesh; the step does not need them)
 }
 
 static int open_device(hnumo_engine *eng, int *ncu) {
@@ -1134,6 +1160,9 @@ static int read_knobs(hnumo_engine *eng, int ncu, Knobs &k) {
       k.glue_perm = !(pg && pg[0] == '0');
     }
   }
+  // float sets: HNUMO_FLOAT_ROWS=1 gives a float's NGL rows to adjacent lanes instead of one lane (same
+  // bits; 4.4x slower at 4 10^5 floats, profiles/r11/floats_cost.json)
+  if (const char *fr = env_knob(eng, "HNUMO_FLOAT_ROWS")) eng->fl_rows = fr[0] == '1';
   return 0;
 }
 
@@ -1342,6 +1371,7 @@ const char *hnumo_last_error(const hnumo_engine *eng) { return eng ? eng->err.c_
 
 static void stats_free(hnumo_engine *eng);
 static void sample_free(hnumo_engine *eng, int id);
+static void floats_free(hnumo_engine *eng, int id);
 
 void hnumo_engine_destroy(hnumo_engine *eng) {
   if (!eng) return;
@@ -1354,6 +1384,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   if (eng->h_diag) (void)hipHostFree(eng->h_diag);
   stats_free(eng);
   for (int id = 0; id < SP_MAXSETS; id++) sample_free(eng, id);
+  for (int id = 0; id < FL_MAXSETS; id++) floats_free(eng, id);
   if (eng->stream && eng->own_stream) (void)hipStreamDestroy(eng->stream);
   if (LocalGroup *g = eng->group) {
     // the destroyed engine cannot take part in exchanges any more; the last one out frees
@@ -1587,6 +1618,9 @@ static int stats_after_step(hnumo_engine *eng);
 // the sample sets' series after a successful step (hnumo_sample_series_begin with every >= 1): after
 // the statistics' own sample of the step, so a set on the statistics sees the new sums
 static int sample_after_step(hnumo_engine *eng);
+// the float sets' advance by params.dt after a successful step (hnumo_floats_begin with every = 1),
+// last: after the statistics' and the sample sets' own work
+static int floats_after_step(hnumo_engine *eng);
 
 int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime_df) {
   if (!eng) return HNUMO_ERR_INVALID;
@@ -1602,7 +1636,8 @@ int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qpri
   if (!eng->resident && (rc = download_state(eng, q_df, qb_df, qprime_df))) return rc;
   rc = stats_after_step(eng);
   const int rs = sample_after_step(eng);
-  return rc ? rc : rs;
+  const int rf = floats_after_step(eng);
+  return rc ? rc : rs ? rs : rf;
 }
 
 int hnumo_set_resident(hnumo_engine *eng, int on) {
@@ -2329,6 +2364,288 @@ int hnumo_sample_destroy(hnumo_engine *eng, int32_t id) {
   return HNUMO_OK;
 }
 
+// ------------------------------------------------------------------ float sets
+// (kernels_float.hip, float_plan.h; plain launches on the engine stream, outside the captured step,
+// like the sample sets: the step's launches, graph and bits are the same with or without sets)
+static void floats_free(hnumo_engine *eng, int id) {
+  auto &s = eng->floats[id];
+  for (void *p : {(void *)s.d_geo, (void *)s.d_nbr, (void *)s.d_f, (void *)s.d_i, (void *)s.d_series})
+    if (p) (void)hipFree(p);
+  s = hnumo_engine::FloatSet{};
+}
+
+// the set `id` of the engine, or nullptr with the message set
+static hnumo_engine::FloatSet *floats_set(hnumo_engine *eng, int32_t id, const char *who) {
+  if (id < 0 || id >= FL_MAXSETS || !eng->floats[id].used) {
+    fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no float set with id " + std::to_string(id));
+    return nullptr;
+  }
+  return &eng->floats[id];
+}
+
+// the plan's floats (sorted order) to the device
+static bool floats_upload(hnumo_engine::FloatSet &s, const FloatPlan &pl) {
+  const size_t M = (size_t)pl.M;
+  bool ok = true;
+  const std::vector<double> *fd[6] = {&pl.x, &pl.y, &pl.wx, &pl.wy, &pl.xi, &pl.eta};
+  for (int v = 0; v < 6; v++) ok = ok && hipMemcpy(s.d_f + v * M, fd[v]->data(), M * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  const std::vector<int32_t> *id[5] = {&pl.elem, &pl.layer, &pl.status, &pl.fresh, &pl.perm};
+  for (int v = 0; v < 5; v++) ok = ok && hipMemcpy(s.d_i + v * M, id[v]->data(), M * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  return ok;
+}
+
+int hnumo_floats_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
+                        const int32_t *layer, int64_t M, int32_t *id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_floats_create";
+  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
+  if (eng->L < 1 || eng->L > MAXL || !float_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
+  if (!eng->fl_nbr_err.empty()) return fail(eng, HNUMO_ERR_INVALID, eng->fl_nbr_err);
+  int slot = -1;
+  for (int i = 0; i < FL_MAXSETS && slot < 0; i++)
+    if (!eng->floats[i].used) slot = i;
+  if (slot < 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the engine holds " + std::to_string(FL_MAXSETS) +
+                                            " float sets already (hnumo_floats_destroy frees one)");
+  FloatGeom geom;
+  if (int rc = float_geometry(coord, ldc, xgl, eng->ngl, eng->nelem_owned, eng->fl_nbr, geom, eng->err)) return rc;
+  FloatPlan pl;
+  if (int rc = float_seed(geom, eng->L, xy, layer, M, pl, eng->err, who)) return rc;
+  HIPCHK(hipSetDevice(eng->device));
+  auto &s = eng->floats[slot];
+  s = hnumo_engine::FloatSet{};
+  const size_t ne = (size_t)geom.ne, m = (size_t)M;
+  bool ok = hipMalloc((void **)&s.d_geo, (9 * ne + 1) * sizeof(double)) == hipSuccess &&
+            hipMalloc((void **)&s.d_nbr, (4 * ne + 1) * sizeof(int)) == hipSuccess &&
+            hipMalloc((void **)&s.d_f, 6 * m * sizeof(double)) == hipSuccess &&
+            hipMalloc((void **)&s.d_i, 5 * m * sizeof(int)) == hipSuccess;
+  if (ok && ne > 0)
+    ok = hipMemcpy(s.d_geo, geom.corners.data(), 8 * ne * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(s.d_geo + 8 * ne, geom.tol.data(), ne * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(s.d_nbr, geom.nbr.data(), 4 * ne * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && floats_upload(s, pl);
+  if (!ok) {
+    (void)hipGetLastError();
+    floats_free(eng, slot);
+    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
+  }
+  s.M = M;
+  s.geom = std::move(geom);
+  s.perm = std::move(pl.perm);
+  s.used = true;
+  *id = slot;
+  return HNUMO_OK;
+}
+
+int hnumo_floats_set(hnumo_engine *eng, int32_t id, const double *xy, const int32_t *layer, int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_set");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_set: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  FloatPlan pl;
+  if (int rc = float_seed(s->geom, eng->L, xy, layer, M, pl, eng->err, "hnumo_floats_set")) return rc;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight writes the old floats)
+  if (!floats_upload(*s, pl)) {
+    (void)hipGetLastError();
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_set: upload failed");
+  }
+  s->perm = std::move(pl.perm);
+  return HNUMO_OK;
+}
+
+static FloatArgs floats_args(hnumo_engine *eng, const hnumo_engine::FloatSet &s) {
+  FloatArgs a{};
+  const size_t ne = (size_t)s.geom.ne, M = (size_t)s.M;
+  a.f.corners = s.d_geo;
+  a.f.tol = s.d_geo + 8 * ne;
+  a.f.nbr = s.d_nbr;
+  a.f.q = eng->q;
+  a.f.npoin = (size_t)eng->npoin;
+  for (int i = 0; i < s.geom.ngl; i++) a.f.xgl[i] = s.geom.xgl[i];
+  a.x = s.d_f, a.y = s.d_f + M, a.wx = s.d_f + 2 * M, a.wy = s.d_f + 3 * M, a.xi = s.d_f + 4 * M, a.eta = s.d_f + 5 * M;
+  a.elem = s.d_i, a.layer = s.d_i + M, a.status = s.d_i + 2 * M, a.fresh = s.d_i + 3 * M, a.perm = s.d_i + 4 * M;
+  a.M = M;
+  return a;
+}
+
+extern "C++" template <int NGL>
+static void floats_launch(hnumo_engine *eng, const FloatArgs &a) {
+  constexpr int G = fl_group(NGL);
+  if (eng->fl_rows)
+    hipLaunchKernelGGL((float_advance_kernel<NGL, G>), dim3((unsigned)((a.M * G + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+                       eng->stream, a);
+  else
+    hipLaunchKernelGGL((float_advance_kernel<NGL, 1>), dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+                       eng->stream, a);
+}
+
+// one record of the set into the series, ordered after what is on the engine stream
+static int floats_record(hnumo_engine *eng, hnumo_engine::FloatSet &s, int id, const char *who) {
+  if (s.count >= s.cap)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series of float set " + std::to_string(id) + " is full (" +
+                                            std::to_string(s.cap) + " records): nothing recorded; read it with clear = 1");
+  FloatArgs a = floats_args(eng, s);
+  a.rec = s.d_series + (size_t)s.count * FL_NREC * (size_t)s.M;
+  hipLaunchKernelGGL(float_record_kernel, dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0, eng->stream, a);
+  HIPCHK(hipGetLastError());
+  s.count++;
+  return HNUMO_OK;
+}
+
+// one advance of the set on the state on the device now, and the record that is due after it
+static int floats_advance(hnumo_engine *eng, hnumo_engine::FloatSet &s, int id, double dt, const char *who) {
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (!float_finite(dt)) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": dt is not finite");
+  FloatArgs a = floats_args(eng, s);
+  a.dt = dt;
+  switch (eng->ngl) {
+    case 3: floats_launch<3>(eng, a); break;
+    case 4: floats_launch<4>(eng, a); break;
+    case 5: floats_launch<5>(eng, a); break;
+    case 6: floats_launch<6>(eng, a); break;
+    default: floats_launch<8>(eng, a); break;
+  }
+  HIPCHK(hipGetLastError());
+  s.advances++;
+  if (s.rec_every > 0 && s.advances % s.rec_every == 0) return floats_record(eng, s, id, who);
+  return HNUMO_OK;
+}
+
+static int floats_after_step(hnumo_engine *eng) {
+  int rc = 0;
+  for (int id = 0; id < FL_MAXSETS; id++) {
+    auto &s = eng->floats[id];
+    if (!s.used || s.every != 1) continue;
+    const int r = floats_advance(eng, s, id, eng->p.dt, "float set after the step (the step itself succeeded)");
+    if (!rc) rc = r;
+  }
+  return rc;
+}
+
+int hnumo_floats_advance(hnumo_engine *eng, int32_t id, double dt) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_advance");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return floats_advance(eng, *s, id, dt, "hnumo_floats_advance");
+}
+
+int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t record_every, int32_t capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_begin");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (every != 0 && every != 1)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: every must be 0 or 1 (a float cannot skip steps), got " + std::to_string(every));
+  if (record_every < 0 || capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: record_every and capacity must be >= 0, got " +
+                                            std::to_string(record_every) + ", " + std::to_string(capacity));
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a record in flight writes the old series)
+  if (s->d_series) (void)hipFree(s->d_series);
+  s->d_series = nullptr;
+  s->every = s->rec_every = s->cap = s->count = 0;
+  s->advances = 0;
+  if (capacity > 0 && hipMalloc((void **)&s->d_series, (size_t)capacity * FL_NREC * (size_t)s->M * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    s->d_series = nullptr;
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_begin: device allocation failed");
+  }
+  s->every = every;
+  s->rec_every = record_every;
+  s->cap = capacity;
+  return HNUMO_OK;
+}
+
+int hnumo_floats_record(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_record");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return floats_record(eng, *s, id, "hnumo_floats_record");
+}
+
+int hnumo_floats_get(hnumo_engine *eng, int32_t id, double *x, double *y, double *u, double *v, int32_t *elem, int32_t *status,
+                     int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_get");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_get: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  HIPCHK(hipSetDevice(eng->device));
+  const size_t m = (size_t)M;
+  std::vector<double> fd(4 * m);
+  std::vector<int32_t> fi(3 * m);
+  HIPCHK(hipMemcpyAsync(fd.data(), s->d_f, 4 * m * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipMemcpyAsync(fi.data(), s->d_i, 3 * m * sizeof(int), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  double *od[4] = {x, y, u, v};
+  for (size_t t = 0; t < m; t++) {
+    const size_t p = (size_t)s->perm[t];
+    for (int c = 0; c < 4; c++)
+      if (od[c]) od[c][p] = fd[c * m + t];
+    if (elem) elem[p] = fi[t];
+    if (status) status[p] = fi[2 * m + t];
+  }
+  return HNUMO_OK;
+}
+
+int hnumo_floats_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_plan");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_plan: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  HIPCHK(hipSetDevice(eng->device));
+  const size_t m = (size_t)M;
+  std::vector<double> fd(2 * m);
+  std::vector<int32_t> fi(m);
+  HIPCHK(hipMemcpyAsync(fd.data(), s->d_f + 4 * m, 2 * m * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipMemcpyAsync(fi.data(), s->d_i, m * sizeof(int), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  for (size_t t = 0; t < m; t++) {
+    const size_t p = (size_t)s->perm[t];
+    if (elem) elem[p] = fi[t];
+    if (xi_eta) xi_eta[2 * p] = fd[t], xi_eta[2 * p + 1] = fd[m + t];
+  }
+  return HNUMO_OK;
+}
+
+int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_series");
+  if (!s) return HNUMO_ERR_INVALID;
+  const int64_t want = (int64_t)FL_NREC * s->M * s->count;
+  if (n < 0 || (out && n < want))
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_series: out holds n = " + std::to_string(n) +
+                                            " values, the series has 5*M*count = " + std::to_string(want));
+  HIPCHK(hipSetDevice(eng->device));
+  if (out && want > 0) {
+    std::vector<double> raw((size_t)want);
+    HIPCHK(hipMemcpyAsync(raw.data(), s->d_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    HIPCHK(hipStreamSynchronize(eng->stream));
+    HIPCHK(hipGetLastError());
+    sample_transpose(raw.data(), FL_NREC, (size_t)s->M, (size_t)s->count, out);
+  }
+  if (count) *count = s->count;
+  if (clear && out) s->count = 0;
+  return HNUMO_OK;
+}
+
+int hnumo_floats_destroy(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!floats_set(eng, id, "hnumo_floats_destroy")) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight uses the set's tables)
+  floats_free(eng, id);
+  return HNUMO_OK;
+}
+
 int hnumo_btp_bcl_coeffs(hnumo_engine *eng, const double *qprime_df) {
   if (!eng) return HNUMO_ERR_INVALID;
   int rc = component_transport_check(eng);
@@ -2707,6 +3024,7 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
     (void)hipSetDevice(engines[i]->device);
     if (int r = stats_after_step(engines[i])) return r;
     if (int r = sample_after_step(engines[i])) return r;
+    if (int r = floats_after_step(engines[i])) return r;
   }
   return 0;
 }

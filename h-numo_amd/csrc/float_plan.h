@@ -1,0 +1,411 @@
+// float_plan.h -- Lagrangian floats advected through the resident state (hnumo_floats_*).
+//
+// Plain C++17, no HIP call: engine.hip and kernels_float.hip include it for the engine,
+// tests/float_plan_main.cpp for a CPU program that runs under the host sanitizers
+// (tests/test_float_plan.py).  It reuses sample_plan.h: the bilinear map, its Newton inverse, the
+// Lagrange weights and the initial location are the sample sets'.
+//
+// A float set is M floats.  A float carries a physical position (x, y), a layer k (1-based, fixed),
+// a stored velocity w = (wx, wy), a cached location (elem, xi, eta) and a status (0 ACTIVE, 1 LEFT --
+// also "not on this rank at creation" --, 2 LOST).  All arithmetic is IEEE double, no FMA
+// (-ffp-contract=off), IEEE division.
+//
+// Velocity of layer k at (e, xi, eta) (float_vel): nodal U(I) = q(2,I,k)/q(1,I,k), V(I) = q(3,I,k)/
+//   q(1,I,k), I = e*P + j*ngl + i; weights Lx, Ly by sample_weights' rule; value = sum_j Ly[j] *
+//   (sum_i Lx[i] * U), both sums left to right from their first product: rows 5(k-1)+2, 5(k-1)+3 of
+//   a hnumo_sample_create_ref set at (elem, xi, eta).
+// Location of a target p starting from element e (float_locate):
+//   1. invert e's bilinear map at p with sample_invert's loop (float_invert: the same statements);
+//      no finite solution: LOST;
+//   2. max(|xi|, |eta|) <= 1 + tol_e: clamp both to [-1,1] and accept;
+//   3. otherwise the side with the larger excess (|xi| - 1 against |eta| - 1, a tie goes to xi; the
+//      sign selects the face): an owned neighbour -> e = neighbour, go to 1; a physical boundary ->
+//      that coordinate = +-1 exactly, p = e's bilinear map at the new (xi, eta) (the float slides
+//      along the wall), go to 1 in the same element; a processor face or a ghost neighbour -> LEFT;
+//   4. each pass through 3 is a hop; a fifth hop: LOST.
+// Advance by dt (float_advance): Heun with the field of the new time level, w from the previous:
+//   if fresh: w = vel(elem, xi, eta), fresh = 0
+//   p* = (x + dt*wx, y + dt*wy);  (e*, xi*, eta*, p*) = locate(p*, elem);  u* = vel(e*, xi*, eta*)
+//   p1 = (x + (0.5*dt)*(wx + u*x), y + (0.5*dt)*(wy + u*y));  (e1, ..) = locate(p1, e*)
+//   w = vel(e1, xi1, eta1);  (x, y) = p1;  (elem, xi, eta) = (e1, xi1, eta1)
+//   A location that ends LEFT or LOST stops the advance: (x, y) = that location's target, elem = 0,
+//   w = 0.  A non-finite velocity gives LOST the same way, (x, y) = the target located last (the
+//   float's own (x, y) for the fresh evaluation).  Inactive floats are never touched again.
+// Every loop is bounded: 32 Newton iterations, 4 hops.
+//
+// The host part: the per-element tables (corners [E][4][2], tol_e [E], side neighbours [E][4] with
+// sides xi=-1, xi=+1, eta=-1, eta=+1: neighbour element, -1 wall, -2 off-rank), derived from face,
+// imapl, imapr by the set of local nodes on each side; validation (every failure: code 4 and a
+// message); the initial location through sample_locate; the stable sort by initial element.
+#pragma once
+#include "sample_plan.h"
+
+#if defined(__HIPCC__)
+#define HNUMO_HD __host__ __device__
+#else
+#define HNUMO_HD
+#endif
+
+namespace hnumo {
+
+constexpr int FL_MAXSETS = 8;
+constexpr int FL_BLOCK = 256;                       // lanes of the kernels' workgroup
+constexpr int FL_ACTIVE = 0, FL_LEFT = 1, FL_LOST = 2;
+constexpr int FL_WALL = -1, FL_OFF_RANK = -2;       // side neighbours that are no element
+constexpr int FL_MAXHOPS = 4, FL_NEWTON = 32;
+constexpr int FL_NREC = 5;                          // a record: x, y, u, v, elem
+
+// what the three functions read: the tables of the owned elements and the state
+struct FloatField {
+  const double *corners;      // [E][4][2]
+  const double *tol;          // [E]
+  const int32_t *nbr;         // [E][4]
+  const double *q;            // q_df(3, npoin, L)
+  size_t npoin;
+  double xgl[8];
+};
+
+// one float, in registers
+struct FloatRec {
+  double x, y, wx, wy, xi, eta;
+  int32_t elem, layer, status, fresh;
+};
+
+HNUMO_HD inline bool float_finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }   // (false for a NaN)
+
+// sample_bilinear on corners c[8] = [4][2]
+HNUMO_HD inline void float_bilinear(const double *c, double xi, double eta, double (&x)[2], double (*J)[2]) {
+  const double w[4] = {0.25 * (1 - xi) * (1 - eta), 0.25 * (1 + xi) * (1 - eta), 0.25 * (1 + xi) * (1 + eta),
+                       0.25 * (1 - xi) * (1 + eta)};
+  for (int d = 0; d < 2; d++) x[d] = w[0] * c[d] + w[1] * c[2 + d] + w[2] * c[4 + d] + w[3] * c[6 + d];
+  if (J)
+    for (int d = 0; d < 2; d++) {
+      J[d][0] = 0.25 * (-(1 - eta) * c[d] + (1 - eta) * c[2 + d] + (1 + eta) * c[4 + d] - (1 + eta) * c[6 + d]);
+      J[d][1] = 0.25 * (-(1 - xi) * c[d] - (1 + xi) * c[2 + d] + (1 + xi) * c[4 + d] + (1 - xi) * c[6 + d]);
+    }
+}
+
+// sample_invert's loop
+HNUMO_HD inline bool float_invert(const double *c, double px, double py, double &xi, double &eta) {
+  xi = eta = 0.0;
+  for (int it = 0; it < FL_NEWTON; it++) {
+    double x[2], J[2][2];
+    float_bilinear(c, xi, eta, x, J);
+    const double rx = px - x[0], ry = py - x[1];
+    const double det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+    const double dxi = (J[1][1] * rx - J[0][1] * ry) / det, deta = (J[0][0] * ry - J[1][0] * rx) / det;
+    if (!float_finite(dxi) || !float_finite(deta)) return false;
+    xi += dxi;
+    eta += deta;
+    if (__builtin_fabs(xi) > 1e3 || __builtin_fabs(eta) > 1e3) return false;
+    if (__builtin_fabs(dxi) <= 1e-16 && __builtin_fabs(deta) <= 1e-16) break;
+  }
+  return true;
+}
+
+// (u, v) of layer k (0-based) at (e, xi, eta), e 0-based
+template <int NGL>
+HNUMO_HD inline void float_vel(const FloatField &f, int k, int e, double xi, double eta, double &u, double &v) {
+  double lx[NGL], ly[NGL];
+#pragma unroll
+  for (int i = 0; i < NGL; i++) {
+    double wx = 1.0, wy = 1.0;
+#pragma unroll
+    for (int m = 0; m < NGL; m++)
+      if (m != i) {
+        wx = wx * ((xi - f.xgl[m]) / (f.xgl[i] - f.xgl[m]));
+        wy = wy * ((eta - f.xgl[m]) / (f.xgl[i] - f.xgl[m]));
+      }
+    lx[i] = wx;
+    ly[i] = wy;
+  }
+  const double *p = f.q + 3 * ((size_t)e * (NGL * NGL) + f.npoin * (size_t)k);
+  u = v = 0.0;
+#pragma unroll
+  for (int j = 0; j < NGL; j++) {
+    const double *r = p + 3 * j * NGL;
+    double ru = lx[0] * (r[1] / r[0]), rv = lx[0] * (r[2] / r[0]);
+#pragma unroll
+    for (int i = 1; i < NGL; i++) {
+      ru = ru + lx[i] * (r[3 * i + 1] / r[3 * i]);
+      rv = rv + lx[i] * (r[3 * i + 2] / r[3 * i]);
+    }
+    u = j == 0 ? ly[0] * ru : u + ly[j] * ru;
+    v = j == 0 ? ly[0] * rv : v + ly[j] * rv;
+  }
+}
+
+// locates (px, py) starting from element e (0-based); on return the element, its clamped (xi, eta)
+// and the target, which a wall may have moved.  Returns the status.
+HNUMO_HD inline int float_locate(const FloatField &f, double &px, double &py, int &e, double &xi, double &eta) {
+  for (int hop = 0;; hop++) {
+    const double *c = f.corners + 8 * (size_t)e;
+    if (!float_invert(c, px, py, xi, eta)) return FL_LOST;
+    const double ax = __builtin_fabs(xi), ay = __builtin_fabs(eta);
+    if ((ax < ay ? ay : ax) <= 1.0 + f.tol[e]) {
+      xi = xi > 1.0 ? 1.0 : xi < -1.0 ? -1.0 : xi;
+      eta = eta > 1.0 ? 1.0 : eta < -1.0 ? -1.0 : eta;
+      return FL_ACTIVE;
+    }
+    if (hop == FL_MAXHOPS) return FL_LOST;
+    const bool in_eta = ay - 1.0 > ax - 1.0;
+    const bool plus = (in_eta ? eta : xi) > 0.0;
+    const int nb = f.nbr[4 * (size_t)e + (in_eta ? 2 : 0) + (plus ? 1 : 0)];
+    if (nb >= 0) {
+      e = nb;
+    } else if (nb == FL_WALL) {
+      (in_eta ? eta : xi) = plus ? 1.0 : -1.0;
+      double x[2];
+      float_bilinear(c, xi, eta, x, nullptr);
+      px = x[0];
+      py = x[1];
+    } else {
+      return FL_LEFT;
+    }
+  }
+}
+
+HNUMO_HD inline void float_stop(FloatRec &r, int status, double px, double py) {
+  r.status = status;
+  r.x = px;
+  r.y = py;
+  r.elem = 0;
+  r.wx = r.wy = 0.0;
+}
+
+// how an evaluation is carried out: by the lane (or host thread) itself; the kernel has a second way
+struct FloatVelPlain {
+  template <int NGL>
+  HNUMO_HD void eval(const FloatField &f, int k, int e, double xi, double eta, double &u, double &v) const {
+    float_vel<NGL>(f, k, e, xi, eta, u, v);
+  }
+};
+
+template <int NGL, class Vel>
+HNUMO_HD inline void float_advance(const FloatField &f, double dt, FloatRec &r, const Vel &vel) {
+  if (r.status != FL_ACTIVE) return;
+  const int k = r.layer - 1;
+  int e = r.elem - 1;
+  if (r.fresh) {
+    vel.template eval<NGL>(f, k, e, r.xi, r.eta, r.wx, r.wy);
+    r.fresh = 0;
+    if (!float_finite(r.wx) || !float_finite(r.wy)) return float_stop(r, FL_LOST, r.x, r.y);
+  }
+  double px = r.x + dt * r.wx, py = r.y + dt * r.wy, xi, eta;
+  int st = float_locate(f, px, py, e, xi, eta);
+  if (st != FL_ACTIVE) return float_stop(r, st, px, py);
+  double us, vs;
+  vel.template eval<NGL>(f, k, e, xi, eta, us, vs);
+  if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py);
+  px = r.x + (0.5 * dt) * (r.wx + us);
+  py = r.y + (0.5 * dt) * (r.wy + vs);
+  st = float_locate(f, px, py, e, xi, eta);
+  if (st != FL_ACTIVE) return float_stop(r, st, px, py);
+  vel.template eval<NGL>(f, k, e, xi, eta, us, vs);
+  if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py);
+  r.x = px;
+  r.y = py;
+  r.wx = us;
+  r.wy = vs;
+  r.elem = e + 1;
+  r.xi = xi;
+  r.eta = eta;
+}
+
+// ------------------------------------------------------------------ the host part
+inline bool float_ngl_ok(int ngl) { return ngl == 3 || ngl == 4 || ngl == 5 || ngl == 6 || ngl == 8; }
+
+// Side neighbours [nelem_owned][4] from face(8,nface), imapl, imapr (3,ngl,nface): the side of an
+// element that a face lies on is read from the local nodes the face lists for that element (all
+// i = 1: xi = -1; all i = ngl: xi = +1; all j = 1: eta = -1; all j = ngl: eta = +1), whatever the
+// mesher's local face numbering and whichever way the two elements meet.
+inline int float_side_neighbours(const int32_t *face, const int32_t *imapl, const int32_t *imapr, int nface, int ngl, int nelem,
+                                 int nelem_owned, std::vector<int32_t> &nbr, std::string &err) {
+  const char *who = "hnumo_floats_create";
+  if (!face || !imapl || !imapr) return err = std::string(who) + ": face, imapl or imapr is NULL", SP_ERR_INVALID;
+  if (ngl < 2 || nelem_owned < 0 || nelem_owned > nelem)
+    return err = std::string(who) + ": ngl must be >= 2 and nelem_owned in 0..nelem", SP_ERR_INVALID;
+  const int32_t UNSET = -3;
+  nbr.assign(4 * (size_t)nelem_owned, UNSET);
+  auto side_of = [&](const int32_t *imap, int f) {
+    bool all[4] = {true, true, true, true};
+    for (int n = 0; n < ngl; n++) {
+      const int32_t i = imap[3 * ((size_t)n + (size_t)ngl * f)], j = imap[3 * ((size_t)n + (size_t)ngl * f) + 1];
+      all[0] = all[0] && i == 1;
+      all[1] = all[1] && i == ngl;
+      all[2] = all[2] && j == 1;
+      all[3] = all[3] && j == ngl;
+    }
+    int s = -1;
+    for (int t = 0; t < 4; t++)
+      if (all[t]) s = s < 0 ? t : 4;
+    return s;
+  };
+  for (int f = 0; f < nface; f++) {
+    const int32_t el = face[8 * (size_t)f + 6], er = face[8 * (size_t)f + 7];
+    if (el < 1 || el > nelem || er > nelem)
+      return err = std::string(who) + ": face(7:8) of face " + std::to_string(f + 1) + " is out of range", SP_ERR_INVALID;
+    for (int lr = 0; lr < 2; lr++) {
+      const int32_t me = lr == 0 ? el : er, other = lr == 0 ? er : el;
+      if (me < 1 || me > nelem_owned) continue;     // (a wall or processor face has no right element; ghosts hold no floats)
+      const int s = side_of(lr == 0 ? imapl : imapr, f);
+      if (s < 0 || s > 3)
+        return err = std::string(who) + ": the nodes of face " + std::to_string(f + 1) + " are not one side of element " +
+                     std::to_string(me),
+               SP_ERR_INVALID;
+      int32_t &slot = nbr[4 * (size_t)(me - 1) + s];
+      if (slot != UNSET)
+        return err = std::string(who) + ": two faces on one side of element " + std::to_string(me) +
+                     " (non-conforming faces are not supported)",
+               SP_ERR_INVALID;
+      slot = lr == 1 ? (other <= nelem_owned ? other - 1 : FL_OFF_RANK)
+                     : er < 0 ? FL_WALL : er == 0 ? FL_OFF_RANK : er <= nelem_owned ? er - 1 : FL_OFF_RANK;
+    }
+  }
+  for (size_t t = 0; t < nbr.size(); t++)
+    if (nbr[t] == UNSET)
+      return err = std::string(who) + ": element " + std::to_string(t / 4 + 1) + " has a side without a face", SP_ERR_INVALID;
+  return 0;
+}
+
+// the tables of the owned elements
+struct FloatGeom {
+  int ngl = 0, ne = 0;
+  double maxc = 0.0;
+  std::vector<double> corners, tol;   // [E][4][2], [E]
+  std::vector<int32_t> nbr;           // [E][4]
+  std::vector<double> coord, xgl;     // coord(2, ne*P) and xgl(ngl): what hnumo_floats_set locates in
+};
+
+// A set in the kernel's order s = 0..M-1: sorted stably by initial element; perm[s] = input position.
+struct FloatPlan {
+  int64_t M = 0;
+  std::vector<int32_t> perm;
+  std::vector<double> x, y, wx, wy, xi, eta;
+  std::vector<int32_t> elem, layer, status, fresh;
+  void get(size_t s, FloatRec &r) const {
+    r = FloatRec{x[s], y[s], wx[s], wy[s], xi[s], eta[s], elem[s], layer[s], status[s], fresh[s]};
+  }
+  void put(size_t s, const FloatRec &r) {
+    x[s] = r.x, y[s] = r.y, wx[s] = r.wx, wy[s] = r.wy, xi[s] = r.xi, eta[s] = r.eta;
+    elem[s] = r.elem, layer[s] = r.layer, status[s] = r.status, fresh[s] = r.fresh;
+  }
+};
+
+// corners, tol_e (sample_locate's) and the kept coord / xgl.  The bilinear-element contract and the
+// rest of the geometry's validation are sample_locate's own, run by float_seed.
+inline int float_geometry(const double *coord, int ldc, const double *xgl, int ngl, int nelem_owned,
+                          const std::vector<int32_t> &nbr, FloatGeom &g, std::string &err) {
+  const char *who = "hnumo_floats_create";
+  if (!coord) return err = std::string(who) + ": coord is NULL", SP_ERR_INVALID;
+  if (ldc != 2 && ldc != 3)
+    return err = std::string(who) + ": ldc must be 2 or 3 (coord(ldc,npoin)), got " + std::to_string(ldc), SP_ERR_INVALID;
+  if (!float_ngl_ok(ngl)) return err = std::string(who) + ": unsupported ngl " + std::to_string(ngl), SP_ERR_INVALID;
+  if (int rc = sample_check_xgl(xgl, ngl, who, err)) return rc;
+  if (nelem_owned < 0 || nbr.size() != 4 * (size_t)nelem_owned)
+    return err = std::string(who) + ": the side neighbours do not cover the owned elements", SP_ERR_INVALID;
+  const int ne = nelem_owned, P = ngl * ngl;
+  g.ngl = ngl;
+  g.ne = ne;
+  g.nbr = nbr;
+  g.xgl.assign(xgl, xgl + ngl);
+  g.coord.resize(2 * (size_t)ne * P);
+  double maxc = 0.0;
+  for (size_t I = 0; I < (size_t)ne * P; I++)
+    for (int d = 0; d < 2; d++) {
+      const double c = coord[(size_t)ldc * I + d], v = std::fabs(c);
+      if (!(v <= std::numeric_limits<double>::max()))
+        return err = std::string(who) + ": coord is not finite at node " + std::to_string(I + 1), SP_ERR_INVALID;
+      g.coord[2 * I + d] = c;
+      maxc = std::max(maxc, v);
+    }
+  g.maxc = maxc;
+  const double tol_x = 64.0 * std::numeric_limits<double>::epsilon() * maxc;
+  g.corners.resize(8 * (size_t)ne);
+  g.tol.resize(ne);
+  for (int e = 0; e < ne; e++) {
+    double c[4][2];
+    sample_corners(g.coord.data(), 2, ngl, e, c);
+    double smin = INFINITY;
+    for (int m = 0; m < 4; m++) {
+      const double ex = c[(m + 1) & 3][0] - c[m][0], ey = c[(m + 1) & 3][1] - c[m][1];
+      smin = std::min(smin, std::sqrt(ex * ex + ey * ey));
+      g.corners[8 * (size_t)e + 2 * m] = c[m][0];
+      g.corners[8 * (size_t)e + 2 * m + 1] = c[m][1];
+    }
+    if (!(smin > 0.0))
+      return err = std::string(who) + ": element " + std::to_string(e + 1) + " has an edge of length 0", SP_ERR_INVALID;
+    g.tol[e] = tol_x / (0.5 * smin);
+  }
+  return 0;
+}
+
+// Seeds (or re-seeds) a set: xy(2,M), layer(M) in 1..nlayers; located through sample_locate; floats no
+// owned element accepts are LEFT; w = 0, fresh = 1; sorted stably by element.
+inline int float_seed(const FloatGeom &g, int nlayers, const double *xy, const int32_t *layer, int64_t M, FloatPlan &p,
+                      std::string &err, const char *who = "hnumo_floats_create") {
+  if (!xy) return err = std::string(who) + ": xy is NULL", SP_ERR_INVALID;
+  if (!layer) return err = std::string(who) + ": layer is NULL", SP_ERR_INVALID;
+  if (M < 1 || M > (int64_t)std::numeric_limits<int32_t>::max())
+    return err = std::string(who) + ": M must be >= 1 (and < 2^31), got " + std::to_string(M), SP_ERR_INVALID;
+  for (int64_t m = 0; m < M; m++)
+    if (layer[m] < 1 || layer[m] > nlayers)
+      return err = std::string(who) + ": layer(" + std::to_string(m + 1) + ") = " + std::to_string(layer[m]) + " is outside 1.." +
+                   std::to_string(nlayers),
+             SP_ERR_INVALID;
+  SamplePlan sp;
+  if (int rc = sample_locate(g.coord.data(), 2, g.xgl.data(), g.ngl, g.ne, xy, M, sp, err, who)) return rc;
+  p.M = M;
+  p.perm.resize(M);
+  for (int64_t m = 0; m < M; m++) p.perm[m] = (int32_t)m;
+  std::stable_sort(p.perm.begin(), p.perm.end(), [&](int32_t a, int32_t b) { return sp.elem[a] < sp.elem[b]; });
+  for (std::vector<double> *v : {&p.x, &p.y, &p.wx, &p.wy, &p.xi, &p.eta}) v->assign(M, 0.0);
+  for (std::vector<int32_t> *v : {&p.elem, &p.layer, &p.status, &p.fresh}) v->assign(M, 0);
+  for (int64_t s = 0; s < M; s++) {
+    const int64_t m = p.perm[s];
+    p.x[s] = xy[2 * m];
+    p.y[s] = xy[2 * m + 1];
+    p.xi[s] = sp.xi_eta[2 * m];
+    p.eta[s] = sp.xi_eta[2 * m + 1];
+    p.elem[s] = sp.elem[m];
+    p.layer[s] = layer[m];
+    p.status[s] = sp.elem[m] > 0 ? FL_ACTIVE : FL_LEFT;
+    p.fresh[s] = 1;
+  }
+  return 0;
+}
+
+// the host statement of one advance of the whole set on a state q_df(3,npoin,L) -- what the kernel runs
+template <int NGL>
+inline void float_advance_all_ngl(const FloatField &f, double dt, FloatPlan &p) {
+  for (int64_t s = 0; s < p.M; s++) {
+    FloatRec r;
+    p.get((size_t)s, r);
+    float_advance<NGL>(f, dt, r, FloatVelPlain{});
+    p.put((size_t)s, r);
+  }
+}
+
+inline FloatField float_field(const FloatGeom &g, const double *q, size_t npoin) {
+  FloatField f{};
+  f.corners = g.corners.data();
+  f.tol = g.tol.data();
+  f.nbr = g.nbr.data();
+  f.q = q;
+  f.npoin = npoin;
+  for (int i = 0; i < g.ngl && i < 8; i++) f.xgl[i] = g.xgl[i];
+  return f;
+}
+
+inline void float_advance_all(const FloatGeom &g, const double *q, size_t npoin, double dt, FloatPlan &p) {
+  const FloatField f = float_field(g, q, npoin);
+  switch (g.ngl) {
+    case 3: float_advance_all_ngl<3>(f, dt, p); break;
+    case 4: float_advance_all_ngl<4>(f, dt, p); break;
+    case 5: float_advance_all_ngl<5>(f, dt, p); break;
+    case 6: float_advance_all_ngl<6>(f, dt, p); break;
+    default: float_advance_all_ngl<8>(f, dt, p); break;
+  }
+}
+
+}  // namespace hnumo

@@ -116,8 +116,7 @@ inline bool sample_invert(const double (&c)[4][2], double px, double py, double 
 
 // Location of xy(2,M) in the owned elements.  Fills p.M, p.ngl, p.maxc, p.elem, p.xi_eta.
 inline int sample_locate(const double *coord, int ldc, const double *xgl, int ngl, int nelem_owned, const double *xy,
-                         int64_t M, SamplePlan &p, std::string &err) {
-  const char *who = "hnumo_sample_create";
+                         int64_t M, SamplePlan &p, std::string &err, const char *who = "hnumo_sample_create") {
   if (!coord) return err = std::string(who) + ": coord is NULL", SP_ERR_INVALID;
   if (!xy) return err = std::string(who) + ": xy is NULL", SP_ERR_INVALID;
   if (ldc != 2 && ldc != 3)

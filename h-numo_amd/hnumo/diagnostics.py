@@ -281,7 +281,7 @@ def restart_state(case, path):
 # ------------------------------------------------------------------ the time loop
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
-              time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1):
+              time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1, floats=None):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
@@ -298,7 +298,13 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     flow_stats: a hnumo.flowstats.DeviceFlowStats or HostFlowStats; after every stats_every-th step
     of this loop it gets add(q).  The device object samples the engine's state where it lives (q is
     ignored, no sync); the host object reads the host arrays, which a resident stepper syncs for it
-    first.  None: nothing changes."""
+    first.  None: nothing changes.
+
+    floats: a hnumo.floats.DeviceFloats or HostFloats (or a list of them); after every step of this
+    loop each gets after_step(q).  A device set that was begun with every = 1 has been advanced by the
+    engine already (no sync); the host object reads the host arrays, which a resident stepper syncs for
+    it first.  None: nothing changes."""
+    float_sets = [] if floats is None else list(floats) if isinstance(floats, (list, tuple)) else [floats]
     if flow_stats is not None and int(stats_every) < 1:
         raise ValueError("stats_every must be >= 1")
     S = case.scalars
@@ -362,6 +368,10 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
             if resident and getattr(flow_stats, "needs_host_state", True):
                 stepper.sync(q, qb, qp)
             flow_stats.add(q)
+        for fs in float_sets:
+            if resident and getattr(fs, "needs_host_state", True):
+                stepper.sync(q, qb, qp)
+            fs.after_step(q)
         if itime % irestart == 0 and dump_data:
             if resident:
                 stepper.sync(q, qb, qp)

@@ -85,6 +85,15 @@ def lib():
         L.hnumo_sample_record.argtypes = [vp, i32]
         L.hnumo_sample_series.argtypes = [vp, i32, dp, i64, C.POINTER(i64), i32]
         L.hnumo_sample_destroy.argtypes = [vp, i32]
+        L.hnumo_floats_create.argtypes = [vp, dp, i32, dp, dp, ip, i64, ip]
+        L.hnumo_floats_get.argtypes = [vp, i32, dp, dp, dp, dp, ip, ip, i64]
+        L.hnumo_floats_plan.argtypes = [vp, i32, ip, dp, i64]
+        L.hnumo_floats_set.argtypes = [vp, i32, dp, ip, i64]
+        L.hnumo_floats_advance.argtypes = [vp, i32, C.c_double]
+        L.hnumo_floats_begin.argtypes = [vp, i32, i32, i32, i32]
+        L.hnumo_floats_record.argtypes = [vp, i32]
+        L.hnumo_floats_series.argtypes = [vp, i32, dp, i64, C.POINTER(i64), i32]
+        L.hnumo_floats_destroy.argtypes = [vp, i32]
         _lib = L
     return _lib
 
@@ -422,6 +431,93 @@ class Engine:
     def sample_destroy(self, sid: int):
         self._check(lib().hnumo_sample_destroy(self.h, int(sid)))
         self._sample_sets.pop(sid, None)
+
+    # ---- float sets on the device state (hnumo_floats_*; mirror and helpers: hnumo/floats.py)
+    @property
+    def _float_sets(self) -> dict:
+        """id -> M of the sets created through this object."""
+        return self.__dict__.setdefault("_float_sets_", {})
+
+    def _floats_M(self, fid: int) -> int:
+        if fid not in self._float_sets:
+            raise EngineError(4, f"no float set with id {fid}")
+        return self._float_sets[fid]
+
+    @staticmethod
+    def _floats_seeds(xy, layer):
+        xy = np.asfortranarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[0] != 2:
+            raise ValueError(f"xy: shape {xy.shape}, expected (2, M)")
+        layer = np.ascontiguousarray(np.broadcast_to(np.asarray(layer, dtype=np.int32), (xy.shape[1],)))
+        return xy, layer
+
+    def floats_create(self, coord, xgl, xy, layer) -> int:
+        """A float set seeded at xy (2, M) in the layers `layer` (M, or one for all; 1-based), located in
+        the owned elements from coord (2 or 3, npoin) and the LGL nodes xgl.  Returns its id."""
+        coord = np.asfortranarray(coord, dtype=np.float64)
+        if coord.ndim != 2 or coord.shape[1] != self.dims["npoin"]:
+            raise ValueError(f"coord: shape {coord.shape}, expected (2 or 3, {self.dims['npoin']})")
+        xgl = self._sample_xgl(xgl)
+        xy, layer = self._floats_seeds(xy, layer)
+        fid = C.c_int32(-1)
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        self._check(lib().hnumo_floats_create(self.h, coord.ctypes.data_as(dp), coord.shape[0], xgl.ctypes.data_as(dp),
+                                              xy.ctypes.data_as(dp), layer.ctypes.data_as(ip), xy.shape[1], C.byref(fid)))
+        self._float_sets[fid.value] = xy.shape[1]
+        return fid.value
+
+    def floats_get(self, fid: int) -> dict:
+        """x, y, u, v (M, float64), elem, status (M, int32) in input order; u, v = the stored velocity."""
+        M = self._floats_M(fid)
+        f = {k: np.zeros(M) for k in ("x", "y", "u", "v")}
+        i = {k: np.zeros(M, dtype=np.int32) for k in ("elem", "status")}
+        ip = C.POINTER(C.c_int32)
+        self._check(lib().hnumo_floats_get(self.h, int(fid), _dp(f["x"]), _dp(f["y"]), _dp(f["u"]), _dp(f["v"]),
+                                           i["elem"].ctypes.data_as(ip), i["status"].ctypes.data_as(ip), M))
+        return {**f, **i}
+
+    def floats_plan(self, fid: int):
+        """(elem (M) int32, xi_eta (2, M)): the floats' cached locations in input order."""
+        M = self._floats_M(fid)
+        elem = np.zeros(M, dtype=np.int32)
+        xe = np.zeros((2, M), order="F")
+        self._check(lib().hnumo_floats_plan(self.h, int(fid), elem.ctypes.data_as(C.POINTER(C.c_int32)), _dp(xe), M))
+        return elem, xe
+
+    def floats_set(self, fid: int, xy, layer):
+        """Re-seed and relocate the set's M floats."""
+        M = self._floats_M(fid)
+        xy, layer = self._floats_seeds(xy, layer)
+        self._check(lib().hnumo_floats_set(self.h, int(fid), xy.ctypes.data_as(C.POINTER(C.c_double)),
+                                           layer.ctypes.data_as(C.POINTER(C.c_int32)), xy.shape[1]))
+
+    def floats_advance(self, fid: int, dt: float):
+        """One advance by dt on the state on the device now; nothing is copied back."""
+        self._check(lib().hnumo_floats_advance(self.h, int(fid), float(dt)))
+
+    def floats_begin(self, fid: int, every: int = 1, record_every: int = 0, capacity: int = 0):
+        """every = 1: the engine advances the set by dt after every successful step.  A record is
+        appended to a series of `capacity` records after every record_every-th advance."""
+        self._check(lib().hnumo_floats_begin(self.h, int(fid), int(every), int(record_every), int(capacity)))
+
+    def floats_record(self, fid: int):
+        """Append one record to the set's series on the device; nothing is copied back."""
+        self._check(lib().hnumo_floats_record(self.h, int(fid)))
+
+    def floats_series(self, fid: int, clear: bool = False):
+        """(5, M, count) = x, y, u, v, elem per record; clear empties the series afterwards."""
+        M = self._floats_M(fid)
+        n = C.c_int64()
+        self._check(lib().hnumo_floats_series(self.h, int(fid), None, 0, C.byref(n), 0))
+        out = np.zeros((5, M, n.value), order="F")
+        if n.value or clear:
+            buf = out if out.size else np.zeros(1)
+            self._check(lib().hnumo_floats_series(self.h, int(fid), _dp(buf), out.size, C.byref(n), int(clear)))
+        return out
+
+    def floats_destroy(self, fid: int):
+        self._check(lib().hnumo_floats_destroy(self.h, int(fid)))
+        self._float_sets.pop(fid, None)
 
     def bench_steps(self, nsteps: int):
         t = C.c_double()

@@ -87,9 +87,12 @@ module hnumo_engine_c
         hnumo_layer_fields, hnumo_stats_begin, hnumo_stats_accumulate, hnumo_stats_sums, &
         hnumo_stats_set_sums, hnumo_stats_fields, hnumo_stats_series, hnumo_stats_end, &
         hnumo_sample_create, hnumo_sample_create_ref, hnumo_sample_plan, hnumo_sample, &
-        hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy
+        hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy, &
+        hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
+        hnumo_floats_begin, hnumo_floats_record, hnumo_floats_series, hnumo_floats_destroy
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
     integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1   ! sample set sources
+    integer(c_int32_t), parameter, public :: HNUMO_FLOAT_ACTIVE = 0, HNUMO_FLOAT_LEFT = 1, HNUMO_FLOAT_LOST = 2   ! float status
 
     interface
         integer(c_int) function hnumo_engine_create(mesh, statics, params, halo, device, eng) &
@@ -372,6 +375,88 @@ module hnumo_engine_c
             type(c_ptr), value :: eng
             integer(c_int32_t), value :: id
         end function hnumo_sample_destroy
+
+        ! Float sets (see include/hnumo_engine.h): Lagrangian floats that live in a layer and move with
+        ! its velocity, advanced on the device after every step.  coord(ldc,npoin) and xgl(ngl) are
+        ! mod_grid's coord and mod_basis' xgl; xy(2,M) the seeds, layer(M) in 1..nlayers.
+        integer(c_int) function hnumo_floats_create(eng, coord, ldc, xgl, xy, layer, M, id) &
+                bind(C, name='hnumo_floats_create')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: coord(*), xgl(*), xy(*)
+            integer(c_int32_t), intent(in) :: layer(*)
+            integer(c_int32_t), value :: ldc
+            integer(c_int64_t), value :: M
+            integer(c_int32_t), intent(out) :: id
+        end function hnumo_floats_create
+
+        ! x, y, u, v, elem, status (M each) in input order; status HNUMO_FLOAT_ACTIVE / LEFT / LOST
+        integer(c_int) function hnumo_floats_get(eng, id, x, y, u, v, elem, status, M) bind(C, name='hnumo_floats_get')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(out) :: x(*), y(*), u(*), v(*)
+            integer(c_int32_t), intent(out) :: elem(*), status(*)
+            integer(c_int64_t), value :: M
+        end function hnumo_floats_get
+
+        ! the cached locations elem(M), xi_eta(2,M) in input order
+        integer(c_int) function hnumo_floats_plan(eng, id, elem, xi_eta, M) bind(C, name='hnumo_floats_plan')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            integer(c_int32_t), intent(out) :: elem(*)
+            real(c_double), intent(out) :: xi_eta(*)
+            integer(c_int64_t), value :: M
+        end function hnumo_floats_plan
+
+        integer(c_int) function hnumo_floats_set(eng, id, xy, layer, M) bind(C, name='hnumo_floats_set')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(in) :: xy(*)
+            integer(c_int32_t), intent(in) :: layer(*)
+            integer(c_int64_t), value :: M
+        end function hnumo_floats_set
+
+        integer(c_int) function hnumo_floats_advance(eng, id, dt) bind(C, name='hnumo_floats_advance')
+            import :: c_int, c_int32_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), value :: dt
+        end function hnumo_floats_advance
+
+        ! every = 1: the engine advances the set by dt after every successful step; a record after every
+        ! record_every-th advance into a series of `capacity` records on the device
+        integer(c_int) function hnumo_floats_begin(eng, id, every, record_every, capacity) &
+                bind(C, name='hnumo_floats_begin')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id, every, record_every, capacity
+        end function hnumo_floats_begin
+
+        integer(c_int) function hnumo_floats_record(eng, id) bind(C, name='hnumo_floats_record')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+        end function hnumo_floats_record
+
+        ! out(5,M,count) = x, y, u, v, elem; n = size(out) >= 5*M*count; clear = 1 empties the series
+        integer(c_int) function hnumo_floats_series(eng, id, out, n, count, clear) bind(C, name='hnumo_floats_series')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: count
+            integer(c_int32_t), value :: clear
+        end function hnumo_floats_series
+
+        integer(c_int) function hnumo_floats_destroy(eng, id) bind(C, name='hnumo_floats_destroy')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+        end function hnumo_floats_destroy
     end interface
 
 contains

@@ -20,8 +20,9 @@
  *     hnumo_create_rhs_btp       -- create_rhs_btp            (mod_rhs_btp.F90:28-59)
  *
  * Around the step, on the device state and without hnumo_sync: the run diagnostics
- * (hnumo_diagnostics) and the online flow statistics -- time means, MKE / EKE, KE series
- * (hnumo_stats_begin .. hnumo_stats_end).
+ * (hnumo_diagnostics), the online flow statistics -- time means, MKE / EKE, KE series
+ * (hnumo_stats_begin .. hnumo_stats_end), sample sets at arbitrary points (hnumo_sample_*) and
+ * Lagrangian floats advected with a layer's velocity (hnumo_floats_*).
  *
  * Layout contract.  Every array is the reference's own Fortran (column-major) array,
  * 1-based integers where the reference is 1-based.  The reference's face arrays carry
@@ -357,6 +358,77 @@ int hnumo_sample_series_begin(hnumo_engine *eng, int32_t id, int32_t every, int3
 int hnumo_sample_record(hnumo_engine *eng, int32_t id);
 int hnumo_sample_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear);
 int hnumo_sample_destroy(hnumo_engine *eng, int32_t id);
+
+/* Float sets (additive in ABI v10): Lagrangian floats or drifters that live in a layer and move with
+ * its velocity, advanced on the device after every step from the resident q_df -- a trajectory needs
+ * the velocity at the float's own position at every step, which the mlswe#### snapshots cannot give
+ * and a host pass pays one hnumo_sync per step for.  DESIGN.md §6.1.3.
+ *
+ * A set is M floats.  A float carries a position (x, y), a layer k (1-based, fixed for life), a stored
+ * velocity w = (wx, wy), a cached location (elem, xi, eta) and a status: HNUMO_FLOAT_ACTIVE,
+ * HNUMO_FLOAT_LEFT (it reached a processor face or a ghost element; also "not on this rank at
+ * creation"), HNUMO_FLOAT_LOST.  All arithmetic is IEEE double without FMA; every value has the bits
+ * of the numpy mirror hnumo/floats.py (HostFloats) on the synced states.
+ *   vel(e, xi, eta): rows 5(k-1)+2, 5(k-1)+3 (u, v of layer k) of a hnumo_sample_create_ref set at
+ *     (e, xi, eta): nodal q(2,I,k)/q(1,I,k), q(3,I,k)/q(1,I,k) under the element's interpolant.
+ *   locate(p, e): (1) invert e's bilinear map at p (Newton from the element centre, at most 32
+ *     iterations, the loop of hnumo_sample_create; no finite solution: LOST); (2) max(|xi|, |eta|) <=
+ *     1 + tol_e (hnumo_sample_create's): clamp to [-1,1], accept; (3) else the side with the larger
+ *     excess (|xi| - 1 against |eta| - 1, a tie goes to xi, the sign selects the face): an owned
+ *     neighbour -> continue there at (1); a physical boundary (face(8) < 0) -> that coordinate = +-1
+ *     exactly and p = e's map at the new (xi, eta) -- the float slides along the wall --, again (1)
+ *     in e; a processor face (face(8) = 0) or a ghost neighbour -> LEFT; (4) a fifth pass through
+ *     (3) -> LOST.
+ *   advance by dt (Heun with the field of the new time level; w is from the previous one):
+ *     if fresh: w = vel(elem, xi, eta), fresh = 0          (first advance after create / set)
+ *     p* = (x + dt*wx, y + dt*wy);  (e*, xi*, eta*, p*) = locate(p*, elem);  u* = vel(e*, xi*, eta*)
+ *     p1 = (x + (0.5*dt)*(wx + u*x), y + (0.5*dt)*(wy + u*y));  (e1, xi1, eta1, p1) = locate(p1, e*)
+ *     w = vel(e1, xi1, eta1);  (x, y) = p1;  (elem, xi, eta) = (e1, xi1, eta1)
+ *     A location that ends LEFT or LOST stops the advance: (x, y) = that location's target, elem = 0,
+ *     w = 0; a non-finite velocity gives LOST likewise, at the target located last.  Inactive floats
+ *     are never touched again.  Moving a LEFT float to the neighbouring rank is the host's job
+ *     (hnumo_floats_get there, hnumo_floats_set / _create here).
+ *
+ * hnumo_floats_create: coord(ldc,npoin), xgl(ngl) as hnumo_sample_create takes them (the same element
+ *   contract and initial location); xy(2,M), layer(M) in 1..nlayers.  Returns the set's id (0..7: up to
+ *   8 sets per engine; hnumo_engine_destroy frees them).  The side neighbours come from the mesh
+ *   descriptor's face / imapl / imapr (the set of local nodes a face lists for an element: any local
+ *   face numbering, either orientation); a mesh they cannot be derived from is an error here.
+ * hnumo_floats_get: x, y, u, v, elem, status (M each, any may be NULL) in input order; u, v = w.
+ * hnumo_floats_plan: the floats' cached locations elem(M), xi_eta(2,M) (either may be NULL) in input
+ *   order: what a hnumo_sample_create_ref set takes.
+ * hnumo_floats_set: re-seeds and relocates the set's M floats; fresh = 1.
+ * hnumo_floats_advance: one advance by dt on the state on the device now.
+ * hnumo_floats_begin: every = 1: the engine advances the set by params.dt after each successful
+ *   hnumo_ti_rk_bcl (hnumo_group_ti_rk_bcl), once the step's abort / retry handling has finished and
+ *   after the statistics' and the sample sets' own work; every = 0: only hnumo_floats_advance does;
+ *   any other value is an error (a float cannot skip steps).  (Re)allocates the series of `capacity`
+ *   records and empties it; a record is appended after every record_every-th advance since begin,
+ *   explicit ones included (0: only hnumo_floats_record appends).  If the series is full then, the
+ *   call returns 4 (the step and the advance are done).
+ * hnumo_floats_record: appends one record to the series on the device; nothing is copied back.
+ * hnumo_floats_series: out(5,M,count) = x, y, u, v, elem (as a double; 0: not on this rank) per record,
+ *   in input order; n = the doubles out can hold; out = NULL (n = 0) only returns count; clear = 1
+ *   empties the series after the copy.
+ * hnumo_floats_destroy: frees the set; its id is given out again.
+ * All launches are plain launches on the engine stream outside the captured step: the step's
+ * launches, graph and bits are the same with or without sets.  All return 4, with a message in
+ * hnumo_last_error, for an unknown id, a wrong M or n, invalid arguments or geometry, a ninth set;
+ * an advance returns 4 before any state was uploaded and for a dt that is not finite.           */
+#define HNUMO_FLOAT_ACTIVE 0
+#define HNUMO_FLOAT_LEFT 1
+#define HNUMO_FLOAT_LOST 2
+int hnumo_floats_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
+                        const int32_t *layer, int64_t M, int32_t *id);
+int hnumo_floats_get(hnumo_engine *eng, int32_t id, double *x, double *y, double *u, double *v, int32_t *elem,
+                     int32_t *status, int64_t M);
+int hnumo_floats_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M);
+int hnumo_floats_set(hnumo_engine *eng, int32_t id, const double *xy, const int32_t *layer, int64_t M);
+int hnumo_floats_advance(hnumo_engine *eng, int32_t id, double dt);
+int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t record_every, int32_t capacity);
+int hnumo_floats_record(hnumo_engine *eng, int32_t id);
+int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear);
+int hnumo_floats_destroy(hnumo_engine *eng, int32_t id);
 
 /* Summation order of the barotropic stage (no reference counterpart: the reference has
  * one order).  HNUMO_SUM_REFERENCE (the default) evaluates the volume integral and the
