@@ -5,9 +5,9 @@
 // baroclinic step (2 barotropic sub-cycles = 2*N_btp*kstages fused stage kernels plus
 // ~20 baroclinic kernels) is captured once into a hipGraph and replayed.  The run diagnostics of
 // the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) and the
-// online flow statistics (kernels_stats.hip: hnumo_stats_*), the sample sets (kernels_sample.hip) and
-// the float sets (kernels_float.hip: hnumo_floats_*) are plain launches on the same stream between
-// replays.
+// online flow statistics (kernels_stats.hip: hnumo_stats_*), the vorticity products (kernels_vort.hip:
+// hnumo_vort_*), the sample sets (kernels_sample.hip) and the float sets (kernels_float.hip:
+// hnumo_floats_*) are plain launches on the same stream between replays.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -33,6 +33,7 @@
 #include "kernels_lapq.hip"
 #include "kernels_diag.hip"
 #include "kernels_stats.hip"
+#include "kernels_vort.hip"
 #include "kernels_sample.hip"
 #include "kernels_float.hip"
 
@@ -199,6 +200,14 @@ struct hnumo_engine {
   double *st_sums = nullptr, *st_part = nullptr, *st_tree[2] = {nullptr, nullptr}, *st_series = nullptr;
   int st_every = 0, st_cap = 0, st_count = 0;
   int64_t st_nsamples = 0, st_steps = 0;
+  // vorticity products (kernels_vort.hip; hnumo_vort_begin .. hnumo_vort_end): the caller's
+  // coriolis_df (NULL: f = 0), the fields of the last sample planar [L][4][npoin], the element
+  // partials [3L][ne] and the two buffers of the tree's passes, the series [capacity][L][3]; series
+  // entries held, successful steps since begin (every > 0: a sample after every every-th one)
+  bool vort_on = false;
+  double *vt_f = nullptr, *vt_fields = nullptr, *vt_part = nullptr, *vt_tree[2] = {nullptr, nullptr}, *vt_series = nullptr;
+  int vt_every = 0, vt_cap = 0, vt_count = 0;
+  int64_t vt_steps = 0;
   // sample sets (kernels_sample.hip; hnumo_sample_*): the host plan (sample_plan.h), its tables on
   // the device, one sample's output [V][M] and the series [capacity][V][M]; series entries held,
   // successful steps since hnumo_sample_series_begin (every > 0: the engine records after every
@@ -1370,6 +1379,7 @@ int hnumo_overrides(const hnumo_engine *eng, char *out, int64_t len) {
 const char *hnumo_last_error(const hnumo_engine *eng) { return eng ? eng->err.c_str() : "null engine"; }
 
 static void stats_free(hnumo_engine *eng);
+static void vort_free(hnumo_engine *eng);
 static void sample_free(hnumo_engine *eng, int id);
 static void floats_free(hnumo_engine *eng, int id);
 
@@ -1383,6 +1393,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   if (eng->h_steps) (void)hipHostFree(eng->h_steps);
   if (eng->h_diag) (void)hipHostFree(eng->h_diag);
   stats_free(eng);
+  vort_free(eng);
   for (int id = 0; id < SP_MAXSETS; id++) sample_free(eng, id);
   for (int id = 0; id < FL_MAXSETS; id++) floats_free(eng, id);
   if (eng->stream && eng->own_stream) (void)hipStreamDestroy(eng->stream);
@@ -1615,6 +1626,9 @@ static int component_transport_check(hnumo_engine *eng) {
 // the flow statistics' sample after a successful step (hnumo_stats_begin with every >= 1; a no-op
 // otherwise): after run_steps returned 0, so a step redone on per-stage launches is sampled once
 static int stats_after_step(hnumo_engine *eng);
+// the vorticity series' sample after a successful step (hnumo_vort_begin with every >= 1): after the
+// statistics' sample, before the sample sets and the floats
+static int vort_after_step(hnumo_engine *eng);
 // the sample sets' series after a successful step (hnumo_sample_series_begin with every >= 1): after
 // the statistics' own sample of the step, so a set on the statistics sees the new sums
 static int sample_after_step(hnumo_engine *eng);
@@ -1635,9 +1649,10 @@ int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qpri
   if (rc) return rc;
   if (!eng->resident && (rc = download_state(eng, q_df, qb_df, qprime_df))) return rc;
   rc = stats_after_step(eng);
+  const int rv = vort_after_step(eng);
   const int rs = sample_after_step(eng);
   const int rf = floats_after_step(eng);
-  return rc ? rc : rs ? rs : rf;
+  return rc ? rc : rv ? rv : rs ? rs : rf;
 }
 
 int hnumo_set_resident(hnumo_engine *eng, int on) {
@@ -2093,6 +2108,194 @@ int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count
   return HNUMO_OK;
 }
 
+// ------------------------------------------------------------------ vorticity products
+// (kernels_vort.hip; plain launches on the engine stream, outside the captured step, like the
+// statistics: the step's launches, graph and bits are the same with or without them)
+static bool sample_ngl_ok(int ngl);
+
+static void vort_free(hnumo_engine *eng) {
+  for (double **p : {&eng->vt_f, &eng->vt_fields, &eng->vt_part, &eng->vt_tree[0], &eng->vt_tree[1], &eng->vt_series}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  eng->vort_on = false;
+  eng->vt_every = eng->vt_cap = eng->vt_count = 0;
+  eng->vt_steps = 0;
+}
+
+static size_t vort_nfields(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
+
+int hnumo_vort_begin(hnumo_engine *eng, const double *coriolis_df, int32_t every, int32_t series_capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (every < 0 || series_capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: every and series_capacity must be >= 0, got " +
+                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: unsupported nlayers or ngl");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
+  vort_free(eng);
+  const int L = eng->L, ne = eng->nelem_owned;
+  auto alloc = [&](double **p, size_t n) { return hipMalloc((void **)p, (n ? n : 1) * sizeof(double)) == hipSuccess; };
+  bool ok = alloc(&eng->vt_fields, vort_nfields(eng));
+  if (coriolis_df) ok = ok && alloc(&eng->vt_f, (size_t)eng->npoin);
+  if (series_capacity > 0) {
+    const size_t nch = ((size_t)ne + ST_CHUNK - 1) / ST_CHUNK;
+    ok = ok && alloc(&eng->vt_part, (size_t)3 * L * ne) && alloc(&eng->vt_tree[0], 3 * L * nch) &&
+         alloc(&eng->vt_tree[1], 3 * L * ((nch + ST_CHUNK - 1) / ST_CHUNK)) &&
+         alloc(&eng->vt_series, (size_t)3 * L * series_capacity);
+  }
+  if (ok && coriolis_df)
+    ok = hipMemcpy(eng->vt_f, coriolis_df, (size_t)eng->npoin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    vort_free(eng);
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_vort_begin: device allocation or upload failed");
+  }
+  // (the nodes of ghost elements are never written: they read 0)
+  HIPCHK(hipMemsetAsync(eng->vt_fields, 0, vort_nfields(eng) * sizeof(double), eng->stream));
+  if (series_capacity > 0)
+    HIPCHK(hipMemsetAsync(eng->vt_series, 0, (size_t)3 * L * series_capacity * sizeof(double), eng->stream));
+  eng->vt_every = every;
+  eng->vt_cap = series_capacity;
+  eng->vort_on = true;
+  return HNUMO_OK;
+}
+
+int hnumo_vort_end(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->vort_on) return HNUMO_OK;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  vort_free(eng);
+  return HNUMO_OK;
+}
+
+extern "C++" template <int NGL, bool SERIES>
+static void vort_launch_L(hnumo_engine *eng, int nb, const VortArgs &a) {
+  switch (eng->L) {
+    case 1: hipLaunchKernelGGL((vort_kernel<NGL, 1, SERIES>), dim3(nb), dim3(VT_BS), 0, eng->stream, a); break;
+    case 2: hipLaunchKernelGGL((vort_kernel<NGL, 2, SERIES>), dim3(nb), dim3(VT_BS), 0, eng->stream, a); break;
+    default: hipLaunchKernelGGL((vort_kernel<NGL, 3, SERIES>), dim3(nb), dim3(VT_BS), 0, eng->stream, a); break;
+  }
+}
+
+extern "C++" template <bool SERIES>
+static void vort_launch_ngl(hnumo_engine *eng, int nb, const VortArgs &a) {
+  switch (eng->ngl) {
+    case 3: vort_launch_L<3, SERIES>(eng, nb, a); break;
+    case 4: vort_launch_L<4, SERIES>(eng, nb, a); break;
+    case 5: vort_launch_L<5, SERIES>(eng, nb, a); break;
+    case 6: vort_launch_L<6, SERIES>(eng, nb, a); break;
+    default: vort_launch_L<8, SERIES>(eng, nb, a); break;
+  }
+}
+
+// the fields of the state on the device into vt_fields, with `series` the next series entry too;
+// ordered after what is on the engine stream, no copy back
+static int vort_form(hnumo_engine *eng, bool series, const char *who) {
+  if (!eng->vort_on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_vort_begin first");
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (series && eng->vt_cap == 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no series (hnumo_vort_begin with series_capacity = 0)");
+  if (series && eng->vt_count >= eng->vt_cap)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series is full (" + std::to_string(eng->vt_cap) +
+                                            " samples): nothing recorded; read it with clear = 1");
+  const int L = eng->L, ne = eng->nelem_owned, EPB = VT_BS / eng->P;
+  if (ne > 0) {
+    VortArgs a{};
+    a.q = eng->q;
+    a.alpha = eng->alpha;
+    a.nstat = eng->nstat;
+    a.f = eng->vt_f;
+    a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
+    a.out = eng->vt_fields;
+    a.part = eng->vt_part;
+    a.gravity = eng->p.gravity;
+    a.npoin = eng->npoin;
+    a.ne = ne;
+    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    if (series)
+      vort_launch_ngl<true>(eng, nb, a);
+    else
+      vort_launch_ngl<false>(eng, nb, a);
+    if (series) {
+      // the tree of the flow statistics' series (stats_sample), over 3L rows
+      const double *in = eng->vt_part;
+      int n = ne, pass = 0;
+      for (;;) {
+        const int nch = (n + ST_CHUNK - 1) / ST_CHUNK;
+        const bool last = nch == 1;
+        double *out = last ? eng->vt_series + (size_t)eng->vt_count * 3 * L : eng->vt_tree[pass & 1];
+        hipLaunchKernelGGL(stats_tree_kernel, dim3(nch, 3 * L), dim3(ST_BS), 0, eng->stream, in, n, out, last ? 1 : nch);
+        if (last) break;
+        in = out;
+        n = nch;
+        pass++;
+      }
+    }
+    HIPCHK(hipGetLastError());
+  }
+  if (series) eng->vt_count++;
+  return HNUMO_OK;
+}
+
+static int vort_after_step(hnumo_engine *eng) {
+  if (!eng->vort_on || eng->vt_every <= 0 || eng->vt_cap == 0) return 0;
+  if (++eng->vt_steps % eng->vt_every) return 0;
+  return vort_form(eng, true, "vorticity series after the step (the step itself succeeded)");
+}
+
+int hnumo_vort_record(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return vort_form(eng, true, "hnumo_vort_record");
+}
+
+int hnumo_vort_fields(hnumo_engine *eng, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->vort_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: call hnumo_vort_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: out is NULL");
+  const size_t want = vort_nfields(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: n must be 4*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  if (int rc = vort_form(eng, false, "hnumo_vort_fields")) return rc;
+  std::vector<double> raw(want);
+  HIPCHK(hipMemcpyAsync(raw.data(), eng->vt_fields, want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  // planar [L][4][npoin] -> the caller's (4,npoin,L)
+  for (int k = 0; k < eng->L; k++)
+    for (int c = 0; c < 4; c++) {
+      const double *r = raw.data() + ((size_t)k * 4 + c) * npoin;
+      double *o = out + 4 * npoin * k + c;
+      for (size_t I = 0; I < npoin; I++) o[4 * I] = r[I];
+    }
+  return HNUMO_OK;
+}
+
+int hnumo_vort_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->vort_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_series: call hnumo_vort_begin first");
+  const int64_t want = 3 * (int64_t)eng->L * eng->vt_count;
+  if (n < 0 || (out && n < want))
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_series: out holds n = " + std::to_string(n) +
+                                            " values, the series has 3*nlayers*count = " + std::to_string(want));
+  HIPCHK(hipSetDevice(eng->device));
+  if (out && want > 0) {
+    HIPCHK(hipMemcpyAsync(out, eng->vt_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    HIPCHK(hipStreamSynchronize(eng->stream));
+    HIPCHK(hipGetLastError());
+  }
+  if (count) *count = eng->vt_count;
+  // (the next sample's slot is written after this copy on the same stream)
+  if (clear && out) eng->vt_count = 0;
+  return HNUMO_OK;
+}
+
 // ------------------------------------------------------------------ sample sets
 // (kernels_sample.hip, sample_plan.h; plain launches on the engine stream, outside the captured
 // step, like the statistics: the step's launches, graph and bits are the same with or without sets)
@@ -2161,9 +2364,11 @@ static int sample_adopt(hnumo_engine *eng, SamplePlan &pl, const double *xgl, in
 
 static int sample_create_checks(hnumo_engine *eng, int32_t source, const int32_t *id, const char *who) {
   if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
-  if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE or HNUMO_SAMPLE_STATS, got " +
-                                            std::to_string(source));
+  if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS && source != HNUMO_SAMPLE_VORT)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS or " +
+                                            "HNUMO_SAMPLE_VORT, got " + std::to_string(source));
+  if (source == HNUMO_SAMPLE_VORT && !eng->vort_on)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": a set on the vorticity products needs f: call hnumo_vort_begin first");
   if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
     return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
   return 0;
@@ -2227,7 +2432,12 @@ static int sample_now(hnumo_engine *eng, const hnumo_engine::SampleSet &s, doubl
     if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the flow statistics: call hnumo_stats_begin first");
     if (eng->st_nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the flow statistics have no samples yet");
   }
+  if (s.source == HNUMO_SAMPLE_VORT && !eng->vort_on)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the vorticity products, which need f: call hnumo_vort_begin first");
   SampleArgs a{};
+  a.nstat = eng->nstat;
+  a.f = eng->vt_f;
+  a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
   a.q = eng->q;
   a.qb = eng->qb;
   a.zbot = eng->nstat + (size_t)NS_ZB * eng->npoin;
@@ -2244,7 +2454,9 @@ static int sample_now(hnumo_engine *eng, const hnumo_engine::SampleSet &s, doubl
   a.out = dst;
   a.npoin = (size_t)eng->npoin;
   a.M = (size_t)s.plan.M;
-  if (s.source == HNUMO_SAMPLE_STATS)
+  if (s.source == HNUMO_SAMPLE_VORT)
+    sample_launch_ngl<SP_SRC_VORT>(eng, s.plan.nchunks(), a);
+  else if (s.source == HNUMO_SAMPLE_STATS)
     sample_launch_ngl<SP_SRC_STATS>(eng, s.plan.nchunks(), a);
   else
     sample_launch_ngl<SP_SRC_STATE>(eng, s.plan.nchunks(), a);
@@ -3023,6 +3235,7 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
   for (int i = 0; i < n; i++) {
     (void)hipSetDevice(engines[i]->device);
     if (int r = stats_after_step(engines[i])) return r;
+    if (int r = vort_after_step(engines[i])) return r;
     if (int r = sample_after_step(engines[i])) return r;
     if (int r = floats_after_step(engines[i])) return r;
   }

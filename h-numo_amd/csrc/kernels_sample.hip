@@ -10,6 +10,13 @@
 //                 (kernels_diag.hip) forms them, rows 5L..5L+3 = qb_df(1:4, I)
 //   source STATS  V = 5L: hbar, um, vm, mke, eke of layer k as stats_fields_kernel (kernels_stats.hip)
 //                 forms them from the sums and the sample count
+//   source VORT   V = 4L: zeta, delta, pv, ow of layer k as vort_node (kernels_vort.hip) forms them from
+//                 the element's own u, v: passes of 256/P whole elements, one lane per node -- the lane
+//                 stores u, v of every layer into the arena (rows 4k+2, 4k+3 of its element, which pv
+//                 and ow overwrite afterwards), barrier, the shared function (zeta, delta to their rows
+//                 at once, pv, ow into registers), barrier, the two rows.  The passes have the same trip count on every lane, so the barriers
+//                 are reached by all; a station set costs its own few elements, not a pass over the
+//                 field
 // Value: val = sum_j Ly[j] * r_j, r_j = sum_i Lx[i] * F(e, j*ngl + i), both sums left to right from
 // their first product.  Points without an element read 0.0.  Built with -ffp-contract=off: no FMA;
 // the host mirror is hnumo/sample.py (HostSampler), equal bit for bit.
@@ -34,14 +41,17 @@ struct SampleArgs {
   const double *q, *qb, *zbot, *alpha;     // q_df(3,npoin,L), qb_df(4,npoin), zbot_df(npoin), alpha_mlswe(L)
   const double2 *sums;                     // the statistics' sums [L][2][npoin] (source STATS)
   double gravity, nsamp;                   // nsamp: the statistics' sample count
+  const double *nstat, *f, *dpsi;          // source VORT: VortArgs' nstat, f (or NULL) and dpsi
   const int *chunk_pt, *chunk_el, *el_list, *slot, *perm;
   const double *w;                         // [2 ngl][M]
   double *out;                             // [V][M]
   size_t npoin, M;
 };
 
+// (the VORT source holds D, h and pv, ow across its barriers: four workgroups per CU leave it the
+// registers for that without scratch at NGL = 8, L = 3; the other sources keep five)
 template <int NGL, int L, int SRC>
-__global__ void __launch_bounds__(SP_CHUNK, 5) sample_kernel(SampleArgs a) {
+__global__ void __launch_bounds__(SP_CHUNK, SRC == SP_SRC_VORT ? 4 : 5) sample_kernel(SampleArgs a) {
   constexpr int P = NGL * NGL, V = sp_nval(L, SRC), ES = sp_estride(NGL, V), K = sp_K(NGL, V);
   static_assert(K >= 1, "the arena holds no element");
   __shared__ double s_f[K * ES];
@@ -50,11 +60,65 @@ __global__ void __launch_bounds__(SP_CHUNK, 5) sample_kernel(SampleArgs a) {
   const size_t npoin = a.npoin;
 
   double ag[L];
-  if (SRC == SP_SRC_STATE) {
+  if (SRC == SP_SRC_STATE || SRC == SP_SRC_VORT) {
 #pragma unroll
     for (int k = 0; k < L; k++) ag[k] = a.alpha[k] / a.gravity;
   }
-  for (int t = tid; t < nel * P; t += SP_CHUNK) {
+  if constexpr (SRC == SP_SRC_VORT) {
+    constexpr int EPI = SP_CHUNK / P;              // whole elements per pass
+    const int le0 = tid / P, ln = tid - le0 * P, j = ln / NGL, i = ln - j * NGL;
+    for (int b = 0; b < nel; b += EPI) {           // (nel is the workgroup's: every lane makes every pass)
+      const int le = b + le0;
+      const bool act = tid < EPI * P && le < nel;
+      double *s = s_f + (act ? le : 0) * ES + ln;
+      size_t I = 0;
+      double h[L], pvow[L][2];
+      if (act) {
+        I = (size_t)a.el_list[el0 + le] * P + ln;
+#pragma unroll
+        for (int k = 0; k < L; k++) {
+          const double *p = a.q + 3 * (I + npoin * k);
+          const double dp = p[0];
+          h[k] = ag[k] * dp;
+          s[(4 * k + 2) * P] = p[1] / dp;
+          s[(4 * k + 3) * P] = p[2] / dp;
+        }
+      }
+      __syncthreads();
+      if (act) {
+        // (D is read here, pass by pass, and zeta, delta go to their own rows at once: fewer
+        // registers live across the barriers)
+        double Di[NGL], Dj[NGL];
+#pragma unroll
+        for (int m = 0; m < NGL; m++) {
+          Di[m] = a.dpsi[m * NGL + i];
+          Dj[m] = a.dpsi[m * NGL + j];
+        }
+        const double ex = a.nstat[(size_t)NS_EX * npoin + I], ey = a.nstat[(size_t)NS_EY * npoin + I];
+        const double nx = a.nstat[(size_t)NS_NX * npoin + I], ny = a.nstat[(size_t)NS_NY * npoin + I];
+        const double f = a.f ? a.f[I] : 0.0;
+        const double *se = s_f + le * ES;
+#pragma unroll
+        for (int k = 0; k < L; k++) {
+          double o[4];
+          vort_node<NGL>(se + (4 * k + 2) * P, se + (4 * k + 3) * P, i, j, Di, Dj, ex, ey, nx, ny, f, h[k], o);
+          s[(4 * k) * P] = o[0];
+          s[(4 * k + 1) * P] = o[1];
+          pvow[k][0] = o[2];
+          pvow[k][1] = o[3];
+        }
+      }
+      __syncthreads();
+      if (act) {
+#pragma unroll
+        for (int k = 0; k < L; k++) {
+          s[(4 * k + 2) * P] = pvow[k][0];
+          s[(4 * k + 3) * P] = pvow[k][1];
+        }
+      }
+    }
+  }
+  for (int t = tid; SRC != SP_SRC_VORT && t < nel * P; t += SP_CHUNK) {
     const int le = t / P, ln = t - le * P;
     const size_t I = (size_t)a.el_list[el0 + le] * P + ln;
     double *s = s_f + le * ES + ln;

@@ -403,7 +403,7 @@ def build_case(cfg: dict, dense: bool = True) -> Case:
         coeff_pbpert_L=coeff_pbpert_L, coeff_pbpert_R=coeff_pbpert_R, coeff_pbub_LR=coeff_pbub_LR,
         coeff_mass_pbub_L=coeff_mass_pbub_L, coeff_mass_pbub_R=coeff_mass_pbub_R,
         coeff_mass_pbpert_LR=coeff_mass_pbpert_LR, alpha=alpha, tau_wind=tau_wind,
-        coriolis_quad=coriolis_quad, grad_zbot_quad=grad_zbot_quad, zbot_df=zbot_df,
+        coriolis_quad=coriolis_quad, coriolis_df=coriolis_df, grad_zbot_quad=grad_zbot_quad, zbot_df=zbot_df,
         zbot_face=zbot_face, fdt2_bcl=fdt2_bcl, a_bcl=a_bcl, b_bcl=b_bcl,
         ssprk_a=ssprk_a, ssprk_beta=ssprk_beta, coord=coord,
         q_df=q_df, qb_df=qb_df, qprime_df=qprime_df,

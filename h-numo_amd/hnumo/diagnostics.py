@@ -281,7 +281,8 @@ def restart_state(case, path):
 # ------------------------------------------------------------------ the time loop
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
-              time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1, floats=None):
+              time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1, floats=None,
+              vorticity=None, vort_every=1):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
@@ -303,7 +304,15 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     floats: a hnumo.floats.DeviceFloats or HostFloats (or a list of them); after every step of this
     loop each gets after_step(q).  A device set that was begun with every = 1 has been advanced by the
     engine already (no sync); the host object reads the host arrays, which a resident stepper syncs for
-    it first.  None: nothing changes."""
+    it first.  None: nothing changes.
+
+    vorticity: a hnumo.vorticity.DeviceVorticity or HostVorticity, handled like flow_stats: after every
+    vort_every-th step of this loop (after flow_stats' sample, before the floats) the host object gets
+    add(q) on the host arrays, which a resident stepper syncs for it first.  A device object was begun
+    with its own `every`: the engine has taken its series sample already (no sync) and the loop leaves
+    it alone.  None: nothing changes."""
+    if vorticity is not None and int(vort_every) < 1:
+        raise ValueError("vort_every must be >= 1")
     float_sets = [] if floats is None else list(floats) if isinstance(floats, (list, tuple)) else [floats]
     if flow_stats is not None and int(stats_every) < 1:
         raise ValueError("stats_every must be >= 1")
@@ -368,6 +377,10 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
             if resident and getattr(flow_stats, "needs_host_state", True):
                 stepper.sync(q, qb, qp)
             flow_stats.add(q)
+        if vorticity is not None and getattr(vorticity, "needs_host_state", True) and nstep % int(vort_every) == 0:
+            if resident:
+                stepper.sync(q, qb, qp)
+            vorticity.add(q)
         for fs in float_sets:
             if resident and getattr(fs, "needs_host_state", True):
                 stepper.sync(q, qb, qp)

@@ -76,6 +76,11 @@ def lib():
         L.hnumo_stats_fields.argtypes = [vp, dp, C.c_int64]
         L.hnumo_stats_series.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]
         L.hnumo_stats_end.argtypes = [vp]
+        L.hnumo_vort_begin.argtypes = [vp, dp, C.c_int32, C.c_int32]
+        L.hnumo_vort_fields.argtypes = [vp, dp, C.c_int64]
+        L.hnumo_vort_record.argtypes = [vp]
+        L.hnumo_vort_series.argtypes = [vp, dp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]
+        L.hnumo_vort_end.argtypes = [vp]
         ip, i32, i64 = C.POINTER(C.c_int32), C.c_int32, C.c_int64
         L.hnumo_sample_create.argtypes = [vp, dp, i32, dp, dp, i64, i32, ip]
         L.hnumo_sample_create_ref.argtypes = [vp, dp, ip, dp, i64, i32, ip]
@@ -113,6 +118,7 @@ def _dp(a, size=None, name="array"):
 SUMMATION = {"reference": 0, "factored": 1}   # HNUMO_SUM_REFERENCE / HNUMO_SUM_FACTORED
 DIAG_MASS = 1                                 # HNUMO_DIAG_MASS
 SAMPLE_STATE, SAMPLE_STATS = 0, 1             # HNUMO_SAMPLE_STATE / HNUMO_SAMPLE_STATS
+SAMPLE_VORT = 2                               # HNUMO_SAMPLE_VORT
 
 
 def unpack_diagnostics(out, L: int) -> dict:
@@ -340,10 +346,46 @@ class Engine:
     def stats_end(self):
         self._check(lib().hnumo_stats_end(self.h))
 
+    # ---- vorticity products of the device state (hnumo_vort_*; mirror: hnumo/vorticity.py)
+    def vort_begin(self, coriolis_df=None, every: int = 0, series: int = 0):
+        """Allocate the buffers (again: reset).  coriolis_df (npoin), or None: f = 0.  every = k >= 1:
+        the engine takes a series sample itself after every k-th successful step; series: samples the
+        series can hold (0: none)."""
+        fp = None
+        if coriolis_df is not None:
+            f = np.ascontiguousarray(np.asarray(coriolis_df, dtype=np.float64).reshape(-1))
+            if f.size != self.dims["npoin"]:
+                raise ValueError(f"coriolis_df: {f.size} elements, expected {self.dims['npoin']}")
+            fp = f.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(lib().hnumo_vort_begin(self.h, fp, int(every), int(series)))
+
+    def vort_fields(self):
+        """(4, npoin, nlayers) = zeta, delta, pv, ow of the state on the device now."""
+        out = np.zeros((4, self.dims["npoin"], self.dims["nlayers"]), order="F")
+        self._check(lib().hnumo_vort_fields(self.h, _dp(out), out.size))
+        return out
+
+    def vort_record(self):
+        """Append one series sample on the device; nothing is copied back."""
+        self._check(lib().hnumo_vort_record(self.h))
+
+    def vort_series(self, clear: bool = False):
+        """(3, nlayers, count) = (Z_k, PZ_k, G_k) per sample; clear empties the series afterwards."""
+        n = C.c_int64()
+        self._check(lib().hnumo_vort_series(self.h, None, 0, C.byref(n), 0))
+        out = np.zeros((3, self.dims["nlayers"], n.value), order="F")
+        if n.value or clear:
+            buf = out if out.size else np.zeros(1)
+            self._check(lib().hnumo_vort_series(self.h, _dp(buf), out.size, C.byref(n), int(clear)))
+        return out
+
+    def vort_end(self):
+        self._check(lib().hnumo_vort_end(self.h))
+
     # ---- sample sets on the device state (hnumo_sample_*; mirror and helpers: hnumo/sample.py)
     def _sample_nval(self, source: int) -> int:
         L = self.dims["nlayers"]
-        return 5 * L if source == SAMPLE_STATS else 5 * L + 4
+        return 4 * L if source == SAMPLE_VORT else 5 * L if source == SAMPLE_STATS else 5 * L + 4
 
     def sample_create(self, coord, xgl, xy, source: int = 0) -> int:
         """A set from physical points xy (2, M), located in the owned elements from coord

@@ -20,6 +20,7 @@ the order of m; Ly[j] from eta likewise.  Nodal fields of element e, node I = e*
     STATE  V = 5L + 4: rows 5k..5k+4 = layer k's h, u, v, dp, elevation as diagnostics.layer_fields
            forms them, rows 5L..5L+3 = qb_df(1:4, I)
     STATS  V = 5L: hbar, um, vm, mke, eke of flowstats' fields per layer
+    VORT   V = 4L: zeta, delta, pv, ow of vorticity's fields per layer
 
 Value: val = sum_j Ly[j] * r_j with r_j = sum_i Lx[i] * F(e, j*ngl + i), both sums left to right
 from their first product.  Points with elem = 0 read 0.0 in every row.  At xi = xgl[a], eta =
@@ -34,6 +35,7 @@ from . import basis as _basis
 from . import diagnostics as _diag
 
 STATE, STATS = 0, 1   # HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS
+VORT = 2              # HNUMO_SAMPLE_VORT
 
 
 def lagrange_weights(xgl, x):
@@ -53,7 +55,7 @@ def lagrange_weights(xgl, x):
 
 
 def nval(nlayers: int, source: int) -> int:
-    return 5 * nlayers if source == STATS else 5 * nlayers + 4
+    return 4 * nlayers if source == VORT else 5 * nlayers if source == STATS else 5 * nlayers + 4
 
 
 def case_xgl(case):
@@ -105,8 +107,12 @@ class HostSampler:
         return out
 
     def _rows(self, f5):
-        """(5, npoin, L) -> (5L, npoin): layer after layer"""
+        """(5 or 4, npoin, L) -> (5L or 4L, npoin): layer after layer"""
         return np.concatenate([f5[:, :, k] for k in range(self.L)], axis=0)
+
+    def sample_vort(self, fields):
+        """(4L, M) from vorticity's fields (4, npoin, L) = HostVorticity.fields(q_df)."""
+        return self._interp(self._rows(np.asarray(fields)))
 
     def sample(self, q_df, qb_df):
         with np.errstate(all="ignore"):                 # (nodes of ghost elements may hold anything)

@@ -86,12 +86,14 @@ module hnumo_engine_c
         hnumo_rccl_unique_id, hnumo_persistent_stats, hnumo_diag_geometry, hnumo_diagnostics, &
         hnumo_layer_fields, hnumo_stats_begin, hnumo_stats_accumulate, hnumo_stats_sums, &
         hnumo_stats_set_sums, hnumo_stats_fields, hnumo_stats_series, hnumo_stats_end, &
+        hnumo_vort_begin, hnumo_vort_fields, hnumo_vort_record, hnumo_vort_series, hnumo_vort_end, &
         hnumo_sample_create, hnumo_sample_create_ref, hnumo_sample_plan, hnumo_sample, &
         hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy, &
         hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
         hnumo_floats_begin, hnumo_floats_record, hnumo_floats_series, hnumo_floats_destroy
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
-    integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1   ! sample set sources
+    integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1, &
+        HNUMO_SAMPLE_VORT = 2   ! sample set sources
     integer(c_int32_t), parameter, public :: HNUMO_FLOAT_ACTIVE = 0, HNUMO_FLOAT_LEFT = 1, HNUMO_FLOAT_LOST = 2   ! float status
 
     interface
@@ -302,6 +304,46 @@ module hnumo_engine_c
             type(c_ptr), value :: eng
         end function hnumo_stats_end
 
+        ! Vorticity products on the device state (see include/hnumo_engine.h): zeta, delta, pv, ow from
+        ! the element's own gradient of the layer velocity, and the enstrophy / potential-enstrophy /
+        ! circulation series, without hnumo_sync.  coriolis_df: c_loc of mod_initial's coriolis_df(npoin),
+        ! or c_null_ptr (f = 0).
+        integer(c_int) function hnumo_vort_begin(eng, coriolis_df, every, series_capacity) &
+                bind(C, name='hnumo_vort_begin')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng, coriolis_df
+            integer(c_int32_t), value :: every, series_capacity
+        end function hnumo_vort_begin
+
+        ! out(4,npoin,nlayers) = zeta, delta, pv, ow; n = 4*npoin*nlayers
+        integer(c_int) function hnumo_vort_fields(eng, out, n) bind(C, name='hnumo_vort_fields')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_vort_fields
+
+        integer(c_int) function hnumo_vort_record(eng) bind(C, name='hnumo_vort_record')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_vort_record
+
+        ! out(3,nlayers,count) = (Z_k, PZ_k, G_k) per sample; n = size(out) >= 3*nlayers*count;
+        ! clear = 1 empties the series after the copy
+        integer(c_int) function hnumo_vort_series(eng, out, n, count, clear) bind(C, name='hnumo_vort_series')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: count
+            integer(c_int32_t), value :: clear
+        end function hnumo_vort_series
+
+        integer(c_int) function hnumo_vort_end(eng) bind(C, name='hnumo_vort_end')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_vort_end
+
         ! Sample sets (see include/hnumo_engine.h): the device state, or the flow statistics, at
         ! arbitrary points by the element's own Lagrange interpolant -- an output grid, a
         ! cross-section, stations -- on demand or after every k-th step into a series on the device.
@@ -337,7 +379,8 @@ module hnumo_engine_c
             integer(c_int64_t), value :: M
         end function hnumo_sample_plan
 
-        ! out(V,M), n = V*M; V = 5*nlayers + 4 (HNUMO_SAMPLE_STATE) or 5*nlayers (HNUMO_SAMPLE_STATS)
+        ! out(V,M), n = V*M; V = 5*nlayers + 4 (HNUMO_SAMPLE_STATE), 5*nlayers (HNUMO_SAMPLE_STATS) or
+        ! 4*nlayers (HNUMO_SAMPLE_VORT)
         integer(c_int) function hnumo_sample(eng, id, out, n) bind(C, name='hnumo_sample')
             import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
             type(c_ptr), value :: eng

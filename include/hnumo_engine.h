@@ -300,6 +300,50 @@ int hnumo_stats_fields(hnumo_engine *eng, double *out, int64_t n);
 int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear);
 int hnumo_stats_end(hnumo_engine *eng);
 
+/* Vorticity products on the device state (additive in ABI v10): relative vorticity, divergence, layer
+ * potential vorticity and the Okubo-Weiss parameter, with the enstrophy, potential-enstrophy and
+ * circulation series -- the diagnostics an eddying run is judged by, which need the gradient of the
+ * layer velocity.  The reference stops short of them (write_output.F90:32,41 allocates `vorticity`
+ * and never fills it), so the arithmetic is defined here.  For an owned element e, layer k and node
+ * (i, j), I = e*P + j*ngl + i (0-based i, j), every sum left to right from its first product, no FMA:
+ *   dp = q(1,I,k);  h = (alpha_k/gravity)*dp (quotient first);  u = q(2,I,k)/dp;  v = q(3,I,k)/dp
+ *   D(m,i) = l_m'(xgl_i) (mod_basis dpsi, as the mesh descriptor passes it)
+ *   u_xi = sum_m D(m,i)*u(m,j);  u_eta = sum_m D(m,j)*u(i,m)          (v likewise)
+ *   u_x = u_xi*ksi_x(I) + u_eta*eta_x(I);  u_y = u_xi*ksi_y(I) + u_eta*eta_y(I)   (v likewise)
+ *   zeta = v_x - u_y;  delta = u_x + v_y;  pv = (zeta + f(I))/h
+ *   sn = u_x - v_y;  ss = v_x + u_y;  ow = (sn*sn + ss*ss) - zeta*zeta
+ * This is the element's own (broken) gradient: no face terms, so no halo and nothing between ranks;
+ * jumps at element edges are not lifted.  Series, per sample and layer, over the rank's owned
+ * elements: Z_k = integral of (0.5*(zeta*zeta))*h, PZ_k = integral of (0.5*(pv*pv))*h, G_k = integral
+ * of zeta, summed exactly as the flow statistics' series (per element the products jac_I * x_I added
+ * in node order, the element sums by the pairwise tree over the element positions; the host adds the
+ * ranks' entries).  Every value has the bits of the numpy mirror hnumo/vorticity.py (HostVorticity) on
+ * the synced state.  Nodes of ghost elements are never formed and read 0.  DESIGN.md §6.1.4.
+ *
+ * hnumo_vort_begin: coriolis_df(npoin) = mod_initial coriolis_df, or NULL: f = 0.  series_capacity:
+ *   samples the series can hold (0: no series).  every = 0: only hnumo_vort_record takes samples;
+ *   every = k >= 1: the engine also takes one after every k-th successful hnumo_ti_rk_bcl
+ *   (hnumo_group_ti_rk_bcl for grouped engines) since begin, once the step's abort / retry handling
+ *   has finished and after the flow statistics' sample, before the sample sets (a VORT set records
+ *   the new state) and the floats.  If that sample finds the series full the step call returns 4 (the
+ *   step is done).  A second call resets.
+ * hnumo_vort_fields: out(4,npoin,nlayers) = zeta, delta, pv, ow in the index order of
+ *   hnumo_layer_fields, n = 4*npoin*nlayers, formed now from the state on the device.
+ * hnumo_vort_record: appends one series sample on the device; nothing is copied back.
+ * hnumo_vort_series: out(3,nlayers,count) = (Z_k, PZ_k, G_k) per sample; n = the doubles out can hold,
+ *   at least 3*nlayers*count; out = NULL (n = 0) only returns count.  clear = 1 empties the series
+ *   after the copy.
+ * hnumo_vort_end: frees the buffers; a no-op before hnumo_vort_begin.
+ * All launches are plain launches on the engine stream outside the captured step: the step's
+ * launches, graph and bits are the same with or without them.  All return 4, with a message in
+ * hnumo_last_error, before hnumo_vort_begin, for a wrong n or negative arguments; a sample returns 4
+ * before any state was uploaded and when the series is full or absent.                         */
+int hnumo_vort_begin(hnumo_engine *eng, const double *coriolis_df, int32_t every, int32_t series_capacity);
+int hnumo_vort_fields(hnumo_engine *eng, double *out, int64_t n);
+int hnumo_vort_record(hnumo_engine *eng);
+int hnumo_vort_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear);
+int hnumo_vort_end(hnumo_engine *eng);
+
 /* Sample sets (additive in ABI v10): the state on the device, or the accumulated flow statistics,
  * evaluated at arbitrary points -- a regular output grid, a cross-section, a few stations -- by the
  * element's own Lagrange interpolant, where the post-processing scripts griddata the synced nodal
@@ -315,6 +359,8 @@ int hnumo_stats_end(hnumo_engine *eng);
  *   HNUMO_SAMPLE_STATE  V = 5*nlayers + 4 values per point: rows 5(k-1)+1..5k = layer k's h, u, v,
  *                       dp, elevation exactly as hnumo_layer_fields forms them, then qb_df(1:4, I)
  *   HNUMO_SAMPLE_STATS  V = 5*nlayers: hbar, um, vm, mke, eke of hnumo_stats_fields per layer
+ *   HNUMO_SAMPLE_VORT   V = 4*nlayers: zeta, delta, pv, ow of hnumo_vort_fields per layer, formed from
+ *                       the set's own elements (f as hnumo_vort_begin took it)
  * Value: val = sum_j Ly[j] * r_j with r_j = sum_i Lx[i] * F(e, j*ngl + i), both sums left to right
  * from their first product (no FMA).  Points with elem = 0 read 0.0 in every row.  At xi = xgl[a],
  * eta = xgl[b] the weights are exactly 0 and 1: the sample is the nodal value.  Every value has the
@@ -345,9 +391,11 @@ int hnumo_stats_end(hnumo_engine *eng);
  * launches, graph and bits are the same with or without sets.  All return 4, with a message in
  * hnumo_last_error, for an unknown id, a wrong n or M, negative arguments, invalid points or
  * geometry, a ninth set; a sample returns 4 before any state was uploaded, when the series is full
- * or absent, and for a STATS set before hnumo_stats_begin or with no statistics samples.        */
+ * or absent, for a STATS set before hnumo_stats_begin or with no statistics samples, and for a VORT
+ * set before hnumo_vort_begin or after hnumo_vort_end (the set needs f: creating it is refused too). */
 #define HNUMO_SAMPLE_STATE 0
 #define HNUMO_SAMPLE_STATS 1
+#define HNUMO_SAMPLE_VORT 2
 int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
                         int64_t M, int32_t source, int32_t *id);
 int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, const int32_t *elem, const double *xi_eta, int64_t M,
