@@ -7,7 +7,8 @@
 // the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) and the
 // online flow statistics (kernels_stats.hip: hnumo_stats_*), the vorticity products (kernels_vort.hip:
 // hnumo_vort_*), the sample sets (kernels_sample.hip) and the float sets (kernels_float.hip:
-// hnumo_floats_*) are plain launches on the same stream between replays.
+// hnumo_floats_*) are plain launches on the same stream between replays; the host side of those four
+// observers is observers.hip, included below.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -21,6 +22,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hnumo_engine.h"
@@ -55,6 +57,21 @@ struct Neighbour {
   int rank = -1, nsend = 0, nrecv = 0;
   int *d_send = nullptr, *d_recv = nullptr;  // 0-based local element ids
   double *sbuf = nullptr, *rbuf = nullptr;
+};
+
+// what the observers of the resident state share (observers.hip).  Series: a ring of `cap` entries
+// of `width` doubles on the device, `count` of them held; every > 0: an entry is due after every
+// every-th of the events counted in `steps` since its begin.  TreeSum: per-element partials
+// [rows][ne] and the two buffers of the passes that sum them into one series entry
+struct Series {
+  double *d = nullptr;
+  size_t width = 0;
+  int every = 0, cap = 0, count = 0;
+  int64_t steps = 0;
+};
+
+struct TreeSum {
+  double *part = nullptr, *tree[2] = {nullptr, nullptr};
 };
 
 struct hnumo_engine {
@@ -192,41 +209,38 @@ struct hnumo_engine {
   const double *diag_w = nullptr;
   double *h_diag = nullptr;                  // pinned copy of diag_out
   double diag_min_dx = 1e16, diag_min_dy = 1e16;
-  // online flow statistics (kernels_stats.hip; hnumo_stats_begin .. hnumo_stats_end): the running
-  // sums [L][2][npoin] pairs, the element partials [2L][ne] and the two buffers of the tree's
-  // passes, the series [capacity][L][2]; samples taken, series entries held, successful steps
-  // since begin (every > 0: the engine samples after every every-th one)
-  bool stats_on = false;
-  double *st_sums = nullptr, *st_part = nullptr, *st_tree[2] = {nullptr, nullptr}, *st_series = nullptr;
-  int st_every = 0, st_cap = 0, st_count = 0;
-  int64_t st_nsamples = 0, st_steps = 0;
-  // vorticity products (kernels_vort.hip; hnumo_vort_begin .. hnumo_vort_end): the caller's
-  // coriolis_df (NULL: f = 0), the fields of the last sample planar [L][4][npoin], the element
-  // partials [3L][ne] and the two buffers of the tree's passes, the series [capacity][L][3]; series
-  // entries held, successful steps since begin (every > 0: a sample after every every-th one)
-  bool vort_on = false;
-  double *vt_f = nullptr, *vt_fields = nullptr, *vt_part = nullptr, *vt_tree[2] = {nullptr, nullptr}, *vt_series = nullptr;
-  int vt_every = 0, vt_cap = 0, vt_count = 0;
-  int64_t vt_steps = 0;
-  // sample sets (kernels_sample.hip; hnumo_sample_*): the host plan (sample_plan.h), its tables on
-  // the device, one sample's output [V][M] and the series [capacity][V][M]; series entries held,
-  // successful steps since hnumo_sample_series_begin (every > 0: the engine records after every
-  // every-th one)
+  // the observers of the resident state (observers.hip), each with the Series it records into.
+  // online flow statistics (hnumo_stats_begin .. hnumo_stats_end): the running sums, the samples taken
+  struct Stats {
+    bool on = false;
+    double *sums = nullptr;
+    int64_t nsamples = 0;
+    TreeSum tree;
+    Series series;
+  } stats;
+  // vorticity products (hnumo_vort_begin .. hnumo_vort_end): the caller's coriolis_df (NULL: f = 0),
+  // the fields of the last sample
+  struct Vort {
+    bool on = false;
+    double *f = nullptr, *fields = nullptr;
+    TreeSum tree;
+    Series series;
+  } vort;
+  // sample sets (hnumo_sample_*): the host plan (sample_plan.h), its tables on the device, one
+  // sample's output [V][M]
   struct SampleSet {
     bool used = false;
     int source = 0, V = 0;
     SamplePlan plan;
     int *d_tab = nullptr;                  // chunk_pt | chunk_el | el_list | slot | perm
     const int *d_chunk_pt = nullptr, *d_chunk_el = nullptr, *d_el_list = nullptr, *d_slot = nullptr, *d_perm = nullptr;
-    double *d_w = nullptr, *d_out = nullptr, *d_series = nullptr;
-    int every = 0, cap = 0, count = 0;
-    int64_t steps = 0;
+    double *d_w = nullptr, *d_out = nullptr;
+    Series series;
   } samples[SP_MAXSETS];
-  // float sets (kernels_float.hip; hnumo_floats_*): the side neighbours of the owned elements, derived
-  // once at create from face / imapl / imapr (fl_nbr_err: why not, reported by hnumo_floats_create);
-  // per set the host geometry (float_plan.h; hnumo_floats_set locates in it), the permutation back to
-  // input order, the element tables and the SoA floats on the device, the series [capacity][5][M];
-  // advances since hnumo_floats_begin (a record after every record_every-th)
+  // float sets (hnumo_floats_*): the side neighbours of the owned elements, derived once at create
+  // from face / imapl / imapr (fl_nbr_err: why not, reported by hnumo_floats_create); per set the host
+  // geometry (float_plan.h), the permutation back to input order, the element tables and the SoA
+  // floats on the device; every: the engine advances the set after a step (its series counts advances)
   std::vector<int32_t> fl_nbr;
   std::string fl_nbr_err;
   bool fl_rows = false;                    // one lane per float; HNUMO_FLOAT_ROWS=1: a row per lane (the mapping not kept)
@@ -239,9 +253,8 @@ struct hnumo_engine {
     int *d_nbr = nullptr;                  // [E][4]
     double *d_f = nullptr;                 // x | y | wx | wy | xi | eta, [M] each
     int *d_i = nullptr;                    // elem | layer | status | fresh | perm, [M] each
-    double *d_series = nullptr;
-    int every = 0, rec_every = 0, cap = 0, count = 0;
-    int64_t advances = 0;
+    int every = 0;
+    Series series;
   } floats[FL_MAXSETS];
 };
 
@@ -1358,6 +1371,9 @@ static int setup_persistent(hnumo_engine *eng, const SetupPlan &pl, const Knobs 
   return 0;
 }
 
+// ------------------------------------------------------------------ observers of the resident state
+#include "observers.hip"
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -1377,11 +1393,6 @@ int hnumo_overrides(const hnumo_engine *eng, char *out, int64_t len) {
 }
 
 const char *hnumo_last_error(const hnumo_engine *eng) { return eng ? eng->err.c_str() : "null engine"; }
-
-static void stats_free(hnumo_engine *eng);
-static void vort_free(hnumo_engine *eng);
-static void sample_free(hnumo_engine *eng, int id);
-static void floats_free(hnumo_engine *eng, int id);
 
 void hnumo_engine_destroy(hnumo_engine *eng) {
   if (!eng) return;
@@ -1623,19 +1634,6 @@ static int component_transport_check(hnumo_engine *eng) {
   return 0;
 }
 
-// the flow statistics' sample after a successful step (hnumo_stats_begin with every >= 1; a no-op
-// otherwise): after run_steps returned 0, so a step redone on per-stage launches is sampled once
-static int stats_after_step(hnumo_engine *eng);
-// the vorticity series' sample after a successful step (hnumo_vort_begin with every >= 1): after the
-// statistics' sample, before the sample sets and the floats
-static int vort_after_step(hnumo_engine *eng);
-// the sample sets' series after a successful step (hnumo_sample_series_begin with every >= 1): after
-// the statistics' own sample of the step, so a set on the statistics sees the new sums
-static int sample_after_step(hnumo_engine *eng);
-// the float sets' advance by params.dt after a successful step (hnumo_floats_begin with every = 1),
-// last: after the statistics' and the sample sets' own work
-static int floats_after_step(hnumo_engine *eng);
-
 int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime_df) {
   if (!eng) return HNUMO_ERR_INVALID;
   if (int rc = component_transport_check(eng)) return rc;
@@ -1648,11 +1646,7 @@ int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qpri
   int rc = run_steps(eng, 1);
   if (rc) return rc;
   if (!eng->resident && (rc = download_state(eng, q_df, qb_df, qprime_df))) return rc;
-  rc = stats_after_step(eng);
-  const int rv = vort_after_step(eng);
-  const int rs = sample_after_step(eng);
-  const int rf = floats_after_step(eng);
-  return rc ? rc : rv ? rv : rs ? rs : rf;
+  return observers_after_step(eng);
 }
 
 int hnumo_set_resident(hnumo_engine *eng, int on) {
@@ -1888,973 +1882,6 @@ int hnumo_layer_fields(hnumo_engine *eng, double *out5, int64_t n) {
   if (err == hipSuccess) err = hipGetLastError();
   (void)hipFree(d);
   HIPCHK(err);
-  return HNUMO_OK;
-}
-
-// ------------------------------------------------------------------ online flow statistics
-// (kernels_stats.hip; plain launches on the engine stream after the step, outside the captured
-// step: the step's launches, graph and bits are the same with statistics on or off)
-static void stats_free(hnumo_engine *eng) {
-  for (double **p : {&eng->st_sums, &eng->st_part, &eng->st_tree[0], &eng->st_tree[1], &eng->st_series}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  eng->stats_on = false;
-  eng->st_every = eng->st_cap = eng->st_count = 0;
-  eng->st_nsamples = eng->st_steps = 0;
-}
-
-static size_t stats_nsums(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
-
-int hnumo_stats_begin(hnumo_engine *eng, int32_t every, int32_t series_capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (every < 0 || series_capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: every and series_capacity must be >= 0, got " +
-                                            std::to_string(every) + ", " + std::to_string(series_capacity));
-  if (eng->L < 1 || eng->L > MAXL || eng->ngl < 2 || eng->ngl * eng->ngl > ST_BS)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: unsupported nlayers or ngl");
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
-  stats_free(eng);
-  const int L = eng->L, ne = eng->nelem_owned;
-  auto alloc = [&](double **p, size_t n) { return hipMalloc((void **)p, (n ? n : 1) * sizeof(double)) == hipSuccess; };
-  bool ok = alloc(&eng->st_sums, stats_nsums(eng));
-  if (series_capacity > 0) {
-    const size_t nch = ((size_t)ne + ST_CHUNK - 1) / ST_CHUNK;
-    ok = ok && alloc(&eng->st_part, (size_t)2 * L * ne) && alloc(&eng->st_tree[0], 2 * L * nch) &&
-         alloc(&eng->st_tree[1], 2 * L * ((nch + ST_CHUNK - 1) / ST_CHUNK)) &&
-         alloc(&eng->st_series, (size_t)2 * L * series_capacity);
-  }
-  if (!ok) {
-    stats_free(eng);
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_stats_begin: device allocation failed");
-  }
-  HIPCHK(hipMemsetAsync(eng->st_sums, 0, stats_nsums(eng) * sizeof(double), eng->stream));
-  if (series_capacity > 0)
-    HIPCHK(hipMemsetAsync(eng->st_series, 0, (size_t)2 * L * series_capacity * sizeof(double), eng->stream));
-  eng->st_every = every;
-  eng->st_cap = series_capacity;
-  eng->stats_on = true;
-  return HNUMO_OK;
-}
-
-int hnumo_stats_end(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats_on) return HNUMO_OK;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  stats_free(eng);
-  return HNUMO_OK;
-}
-
-#define STATS_LAUNCH(L_)                                                                                       \
-  do {                                                                                                         \
-    if (series)                                                                                                \
-      hipLaunchKernelGGL((stats_accumulate_kernel<L_, true>), dim3(nb), dim3(ST_BS), 0, eng->stream, a);       \
-    else                                                                                                       \
-      hipLaunchKernelGGL((stats_accumulate_kernel<L_, false>), dim3(nb), dim3(ST_BS), 0, eng->stream, a);      \
-  } while (0)
-
-// one sample of the state on the device, ordered after what is on the engine stream; no copy back
-static int stats_sample(hnumo_engine *eng, const char *who) {
-  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_stats_begin first");
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  const bool series = eng->st_cap > 0;
-  if (series && eng->st_count >= eng->st_cap)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series is full (" + std::to_string(eng->st_cap) +
-                                            " samples): nothing accumulated; read it with clear = 1");
-  const int L = eng->L, ne = eng->nelem_owned, EPB = ST_BS / eng->P;
-  if (ne > 0) {
-    StatsArgs a{};
-    a.q = eng->q;
-    a.alpha = eng->alpha;
-    a.w = eng->nstat + (size_t)NS_W * eng->npoin;
-    a.sums = (double2 *)eng->st_sums;
-    a.part = eng->st_part;
-    a.gravity = eng->p.gravity;
-    a.npoin = eng->npoin;
-    a.ne = ne;
-    a.ngl = eng->ngl;
-    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
-    switch (L) {
-      case 1: STATS_LAUNCH(1); break;
-      case 2: STATS_LAUNCH(2); break;
-      default: STATS_LAUNCH(3); break;
-    }
-    if (series) {
-      // the tree: passes over aligned chunks until one value per row is left, which the last pass
-      // writes into the sample's slot of the series
-      const double *in = eng->st_part;
-      int n = ne, pass = 0;
-      for (;;) {
-        const int nch = (n + ST_CHUNK - 1) / ST_CHUNK;
-        const bool last = nch == 1;
-        double *out = last ? eng->st_series + (size_t)eng->st_count * 2 * L : eng->st_tree[pass & 1];
-        hipLaunchKernelGGL(stats_tree_kernel, dim3(nch, 2 * L), dim3(ST_BS), 0, eng->stream, in, n, out, last ? 1 : nch);
-        if (last) break;
-        in = out;
-        n = nch;
-        pass++;
-      }
-    }
-    HIPCHK(hipGetLastError());
-  }
-  if (series) eng->st_count++;
-  eng->st_nsamples++;
-  return HNUMO_OK;
-}
-
-static int stats_after_step(hnumo_engine *eng) {
-  if (!eng->stats_on || eng->st_every <= 0) return 0;
-  if (++eng->st_steps % eng->st_every) return 0;
-  return stats_sample(eng, "flow statistics after the step (the step itself succeeded)");
-}
-
-int hnumo_stats_accumulate(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  return stats_sample(eng, "hnumo_stats_accumulate");
-}
-
-// the sums between the device layout [L][2][npoin][2] and the caller's (4,npoin,L)
-int hnumo_stats_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: call hnumo_stats_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: out is NULL");
-  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
-  HIPCHK(hipSetDevice(eng->device));
-  std::vector<double> raw(want);
-  HIPCHK(hipMemcpyAsync(raw.data(), eng->st_sums, want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  for (int k = 0; k < eng->L; k++)
-    for (int p = 0; p < 2; p++)
-      for (size_t I = 0; I < npoin; I++)
-        for (int j = 0; j < 2; j++) out[4 * (I + npoin * k) + 2 * p + j] = raw[2 * st_pair(k, p, I, npoin) + j];
-  if (nsamples) *nsamples = eng->st_nsamples;
-  return HNUMO_OK;
-}
-
-int hnumo_stats_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: call hnumo_stats_begin first");
-  if (!in) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: in is NULL");
-  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
-  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: nsamples must be >= 0");
-  HIPCHK(hipSetDevice(eng->device));
-  std::vector<double> raw(want);
-  for (int k = 0; k < eng->L; k++)
-    for (int p = 0; p < 2; p++)
-      for (size_t I = 0; I < npoin; I++)
-        for (int j = 0; j < 2; j++) raw[2 * st_pair(k, p, I, npoin) + j] = in[4 * (I + npoin * k) + 2 * p + j];
-  HIPCHK(hipMemcpyAsync(eng->st_sums, raw.data(), want * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  eng->st_nsamples = nsamples;
-  return HNUMO_OK;
-}
-
-int hnumo_stats_fields(hnumo_engine *eng, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: call hnumo_stats_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: out is NULL");
-  const int64_t want = 5 * (int64_t)eng->npoin * eng->L;
-  if (n != want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: n must be 5*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
-  if (eng->st_nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: no samples yet");
-  HIPCHK(hipSetDevice(eng->device));
-  double *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
-  const size_t npoin = (size_t)eng->npoin, nown = (size_t)eng->nelem_owned * eng->P;
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((npoin + ST_BS - 1) / ST_BS, 4096));
-  const double2 *s = (const double2 *)eng->st_sums;
-  const double ns = (double)eng->st_nsamples;
-  switch (eng->L) {
-    case 1: hipLaunchKernelGGL(stats_fields_kernel<1>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d); break;
-    case 2: hipLaunchKernelGGL(stats_fields_kernel<2>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d); break;
-    default: hipLaunchKernelGGL(stats_fields_kernel<3>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d); break;
-  }
-  hipError_t err = hipMemcpyAsync(out, d, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(eng->stream);
-  if (err == hipSuccess) err = hipGetLastError();
-  (void)hipFree(d);
-  HIPCHK(err);
-  return HNUMO_OK;
-}
-
-int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_series: call hnumo_stats_begin first");
-  const int64_t want = 2 * (int64_t)eng->L * eng->st_count;
-  if (n < 0 || (out && n < want))
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_series: out holds n = " + std::to_string(n) +
-                                            " values, the series has 2*nlayers*count = " + std::to_string(want));
-  HIPCHK(hipSetDevice(eng->device));
-  if (out && want > 0) {
-    HIPCHK(hipMemcpyAsync(out, eng->st_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    HIPCHK(hipStreamSynchronize(eng->stream));
-    HIPCHK(hipGetLastError());
-  }
-  if (count) *count = eng->st_count;
-  // (the next sample's slot is written after this copy on the same stream)
-  if (clear && out) eng->st_count = 0;
-  return HNUMO_OK;
-}
-
-// ------------------------------------------------------------------ vorticity products
-// (kernels_vort.hip; plain launches on the engine stream, outside the captured step, like the
-// statistics: the step's launches, graph and bits are the same with or without them)
-static bool sample_ngl_ok(int ngl);
-
-static void vort_free(hnumo_engine *eng) {
-  for (double **p : {&eng->vt_f, &eng->vt_fields, &eng->vt_part, &eng->vt_tree[0], &eng->vt_tree[1], &eng->vt_series}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  eng->vort_on = false;
-  eng->vt_every = eng->vt_cap = eng->vt_count = 0;
-  eng->vt_steps = 0;
-}
-
-static size_t vort_nfields(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
-
-int hnumo_vort_begin(hnumo_engine *eng, const double *coriolis_df, int32_t every, int32_t series_capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (every < 0 || series_capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: every and series_capacity must be >= 0, got " +
-                                            std::to_string(every) + ", " + std::to_string(series_capacity));
-  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: unsupported nlayers or ngl");
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
-  vort_free(eng);
-  const int L = eng->L, ne = eng->nelem_owned;
-  auto alloc = [&](double **p, size_t n) { return hipMalloc((void **)p, (n ? n : 1) * sizeof(double)) == hipSuccess; };
-  bool ok = alloc(&eng->vt_fields, vort_nfields(eng));
-  if (coriolis_df) ok = ok && alloc(&eng->vt_f, (size_t)eng->npoin);
-  if (series_capacity > 0) {
-    const size_t nch = ((size_t)ne + ST_CHUNK - 1) / ST_CHUNK;
-    ok = ok && alloc(&eng->vt_part, (size_t)3 * L * ne) && alloc(&eng->vt_tree[0], 3 * L * nch) &&
-         alloc(&eng->vt_tree[1], 3 * L * ((nch + ST_CHUNK - 1) / ST_CHUNK)) &&
-         alloc(&eng->vt_series, (size_t)3 * L * series_capacity);
-  }
-  if (ok && coriolis_df)
-    ok = hipMemcpy(eng->vt_f, coriolis_df, (size_t)eng->npoin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    vort_free(eng);
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_vort_begin: device allocation or upload failed");
-  }
-  // (the nodes of ghost elements are never written: they read 0)
-  HIPCHK(hipMemsetAsync(eng->vt_fields, 0, vort_nfields(eng) * sizeof(double), eng->stream));
-  if (series_capacity > 0)
-    HIPCHK(hipMemsetAsync(eng->vt_series, 0, (size_t)3 * L * series_capacity * sizeof(double), eng->stream));
-  eng->vt_every = every;
-  eng->vt_cap = series_capacity;
-  eng->vort_on = true;
-  return HNUMO_OK;
-}
-
-int hnumo_vort_end(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->vort_on) return HNUMO_OK;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  vort_free(eng);
-  return HNUMO_OK;
-}
-
-extern "C++" template <int NGL, bool SERIES>
-static void vort_launch_L(hnumo_engine *eng, int nb, const VortArgs &a) {
-  switch (eng->L) {
-    case 1: hipLaunchKernelGGL((vort_kernel<NGL, 1, SERIES>), dim3(nb), dim3(VT_BS), 0, eng->stream, a); break;
-    case 2: hipLaunchKernelGGL((vort_kernel<NGL, 2, SERIES>), dim3(nb), dim3(VT_BS), 0, eng->stream, a); break;
-    default: hipLaunchKernelGGL((vort_kernel<NGL, 3, SERIES>), dim3(nb), dim3(VT_BS), 0, eng->stream, a); break;
-  }
-}
-
-extern "C++" template <bool SERIES>
-static void vort_launch_ngl(hnumo_engine *eng, int nb, const VortArgs &a) {
-  switch (eng->ngl) {
-    case 3: vort_launch_L<3, SERIES>(eng, nb, a); break;
-    case 4: vort_launch_L<4, SERIES>(eng, nb, a); break;
-    case 5: vort_launch_L<5, SERIES>(eng, nb, a); break;
-    case 6: vort_launch_L<6, SERIES>(eng, nb, a); break;
-    default: vort_launch_L<8, SERIES>(eng, nb, a); break;
-  }
-}
-
-// the fields of the state on the device into vt_fields, with `series` the next series entry too;
-// ordered after what is on the engine stream, no copy back
-static int vort_form(hnumo_engine *eng, bool series, const char *who) {
-  if (!eng->vort_on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_vort_begin first");
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  if (series && eng->vt_cap == 0)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no series (hnumo_vort_begin with series_capacity = 0)");
-  if (series && eng->vt_count >= eng->vt_cap)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series is full (" + std::to_string(eng->vt_cap) +
-                                            " samples): nothing recorded; read it with clear = 1");
-  const int L = eng->L, ne = eng->nelem_owned, EPB = VT_BS / eng->P;
-  if (ne > 0) {
-    VortArgs a{};
-    a.q = eng->q;
-    a.alpha = eng->alpha;
-    a.nstat = eng->nstat;
-    a.f = eng->vt_f;
-    a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
-    a.out = eng->vt_fields;
-    a.part = eng->vt_part;
-    a.gravity = eng->p.gravity;
-    a.npoin = eng->npoin;
-    a.ne = ne;
-    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
-    if (series)
-      vort_launch_ngl<true>(eng, nb, a);
-    else
-      vort_launch_ngl<false>(eng, nb, a);
-    if (series) {
-      // the tree of the flow statistics' series (stats_sample), over 3L rows
-      const double *in = eng->vt_part;
-      int n = ne, pass = 0;
-      for (;;) {
-        const int nch = (n + ST_CHUNK - 1) / ST_CHUNK;
-        const bool last = nch == 1;
-        double *out = last ? eng->vt_series + (size_t)eng->vt_count * 3 * L : eng->vt_tree[pass & 1];
-        hipLaunchKernelGGL(stats_tree_kernel, dim3(nch, 3 * L), dim3(ST_BS), 0, eng->stream, in, n, out, last ? 1 : nch);
-        if (last) break;
-        in = out;
-        n = nch;
-        pass++;
-      }
-    }
-    HIPCHK(hipGetLastError());
-  }
-  if (series) eng->vt_count++;
-  return HNUMO_OK;
-}
-
-static int vort_after_step(hnumo_engine *eng) {
-  if (!eng->vort_on || eng->vt_every <= 0 || eng->vt_cap == 0) return 0;
-  if (++eng->vt_steps % eng->vt_every) return 0;
-  return vort_form(eng, true, "vorticity series after the step (the step itself succeeded)");
-}
-
-int hnumo_vort_record(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  return vort_form(eng, true, "hnumo_vort_record");
-}
-
-int hnumo_vort_fields(hnumo_engine *eng, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->vort_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: call hnumo_vort_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: out is NULL");
-  const size_t want = vort_nfields(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: n must be 4*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
-  HIPCHK(hipSetDevice(eng->device));
-  if (int rc = vort_form(eng, false, "hnumo_vort_fields")) return rc;
-  std::vector<double> raw(want);
-  HIPCHK(hipMemcpyAsync(raw.data(), eng->vt_fields, want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  // planar [L][4][npoin] -> the caller's (4,npoin,L)
-  for (int k = 0; k < eng->L; k++)
-    for (int c = 0; c < 4; c++) {
-      const double *r = raw.data() + ((size_t)k * 4 + c) * npoin;
-      double *o = out + 4 * npoin * k + c;
-      for (size_t I = 0; I < npoin; I++) o[4 * I] = r[I];
-    }
-  return HNUMO_OK;
-}
-
-int hnumo_vort_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->vort_on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_series: call hnumo_vort_begin first");
-  const int64_t want = 3 * (int64_t)eng->L * eng->vt_count;
-  if (n < 0 || (out && n < want))
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_series: out holds n = " + std::to_string(n) +
-                                            " values, the series has 3*nlayers*count = " + std::to_string(want));
-  HIPCHK(hipSetDevice(eng->device));
-  if (out && want > 0) {
-    HIPCHK(hipMemcpyAsync(out, eng->vt_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    HIPCHK(hipStreamSynchronize(eng->stream));
-    HIPCHK(hipGetLastError());
-  }
-  if (count) *count = eng->vt_count;
-  // (the next sample's slot is written after this copy on the same stream)
-  if (clear && out) eng->vt_count = 0;
-  return HNUMO_OK;
-}
-
-// ------------------------------------------------------------------ sample sets
-// (kernels_sample.hip, sample_plan.h; plain launches on the engine stream, outside the captured
-// step, like the statistics: the step's launches, graph and bits are the same with or without sets)
-static void sample_free(hnumo_engine *eng, int id) {
-  auto &s = eng->samples[id];
-  if (s.d_tab) (void)hipFree(s.d_tab);
-  for (double **p : {&s.d_w, &s.d_out, &s.d_series})
-    if (*p) (void)hipFree(*p);
-  s = hnumo_engine::SampleSet{};
-}
-
-static bool sample_ngl_ok(int ngl) { return ngl == 3 || ngl == 4 || ngl == 5 || ngl == 6 || ngl == 8; }
-
-// the set `id` of the engine, or nullptr with the message set
-static hnumo_engine::SampleSet *sample_set(hnumo_engine *eng, int32_t id, const char *who) {
-  if (id < 0 || id >= SP_MAXSETS || !eng->samples[id].used) {
-    fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no sample set with id " + std::to_string(id));
-    return nullptr;
-  }
-  return &eng->samples[id];
-}
-
-// the located or given points of `pl` become a set: tables built and uploaded
-static int sample_adopt(hnumo_engine *eng, SamplePlan &pl, const double *xgl, int32_t source, int32_t *id, const char *who) {
-  int slot = -1;
-  for (int i = 0; i < SP_MAXSETS && slot < 0; i++)
-    if (!eng->samples[i].used) slot = i;
-  if (slot < 0)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the engine holds " + std::to_string(SP_MAXSETS) +
-                                            " sample sets already (hnumo_sample_destroy frees one)");
-  const int V = sp_nval(eng->L, source);
-  sample_chunks(xgl, sp_K(eng->ngl, V), pl);
-  HIPCHK(hipSetDevice(eng->device));
-  auto &s = eng->samples[slot];
-  s = hnumo_engine::SampleSet{};
-  const size_t M = (size_t)pl.M, nch = (size_t)pl.nchunks(), nel = pl.el_list.size();
-  const size_t ntab = 2 * (nch + 1) + nel + 2 * M;
-  std::vector<int> tab;
-  tab.reserve(ntab);
-  for (const std::vector<int32_t> *v : {&pl.chunk_pt, &pl.chunk_el, &pl.el_list, &pl.slot, &pl.perm})
-    tab.insert(tab.end(), v->begin(), v->end());
-  bool ok = hipMalloc((void **)&s.d_tab, ntab * sizeof(int)) == hipSuccess &&
-            hipMalloc((void **)&s.d_w, pl.w.size() * sizeof(double)) == hipSuccess &&
-            hipMalloc((void **)&s.d_out, (size_t)V * M * sizeof(double)) == hipSuccess;
-  ok = ok && hipMemcpy(s.d_tab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(s.d_w, pl.w.data(), pl.w.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    sample_free(eng, slot);
-    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
-  }
-  s.d_chunk_pt = s.d_tab;
-  s.d_chunk_el = s.d_chunk_pt + nch + 1;
-  s.d_el_list = s.d_chunk_el + nch + 1;
-  s.d_slot = s.d_el_list + nel;
-  s.d_perm = s.d_slot + M;
-  s.source = source;
-  s.V = V;
-  s.plan = std::move(pl);
-  s.plan.w = std::vector<double>();   // (the device holds the weights and the work lists)
-  s.plan.slot = s.plan.perm = std::vector<int32_t>();
-  s.used = true;
-  *id = slot;
-  return HNUMO_OK;
-}
-
-static int sample_create_checks(hnumo_engine *eng, int32_t source, const int32_t *id, const char *who) {
-  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
-  if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS && source != HNUMO_SAMPLE_VORT)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS or " +
-                                            "HNUMO_SAMPLE_VORT, got " + std::to_string(source));
-  if (source == HNUMO_SAMPLE_VORT && !eng->vort_on)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": a set on the vorticity products needs f: call hnumo_vort_begin first");
-  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
-  return 0;
-}
-
-int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy, int64_t M,
-                        int32_t source, int32_t *id) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create")) return rc;
-  SamplePlan pl;
-  if (int rc = sample_locate(coord, ldc, xgl, eng->ngl, eng->nelem_owned, xy, M, pl, eng->err)) return rc;
-  return sample_adopt(eng, pl, xgl, source, id, "hnumo_sample_create");
-}
-
-int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, const int32_t *elem, const double *xi_eta, int64_t M,
-                            int32_t source, int32_t *id) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create_ref")) return rc;
-  SamplePlan pl;
-  if (int rc = sample_take_ref(xgl, eng->ngl, eng->nelem_owned, elem, xi_eta, M, pl, eng->err)) return rc;
-  return sample_adopt(eng, pl, xgl, source, id, "hnumo_sample_create_ref");
-}
-
-int hnumo_sample_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  const auto *s = sample_set(eng, id, "hnumo_sample_plan");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->plan.M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_plan: M must be the set's " + std::to_string(s->plan.M) + ", got " +
-                                            std::to_string(M));
-  if (elem) std::memcpy(elem, s->plan.elem.data(), (size_t)M * sizeof(int32_t));
-  if (xi_eta) std::memcpy(xi_eta, s->plan.xi_eta.data(), 2 * (size_t)M * sizeof(double));
-  return HNUMO_OK;
-}
-
-extern "C++" template <int NGL, int SRC>
-static void sample_launch_L(hnumo_engine *eng, int nch, const SampleArgs &a) {
-  switch (eng->L) {
-    case 1: hipLaunchKernelGGL((sample_kernel<NGL, 1, SRC>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a); break;
-    case 2: hipLaunchKernelGGL((sample_kernel<NGL, 2, SRC>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a); break;
-    default: hipLaunchKernelGGL((sample_kernel<NGL, 3, SRC>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a); break;
-  }
-}
-
-extern "C++" template <int SRC>
-static void sample_launch_ngl(hnumo_engine *eng, int nch, const SampleArgs &a) {
-  switch (eng->ngl) {
-    case 3: sample_launch_L<3, SRC>(eng, nch, a); break;
-    case 4: sample_launch_L<4, SRC>(eng, nch, a); break;
-    case 5: sample_launch_L<5, SRC>(eng, nch, a); break;
-    case 6: sample_launch_L<6, SRC>(eng, nch, a); break;
-    default: sample_launch_L<8, SRC>(eng, nch, a); break;
-  }
-}
-
-// one sample of the set into `dst` [V][M] on the device, ordered after what is on the engine stream
-static int sample_now(hnumo_engine *eng, const hnumo_engine::SampleSet &s, double *dst, const char *who) {
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  if (s.source == HNUMO_SAMPLE_STATS) {
-    if (!eng->stats_on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the flow statistics: call hnumo_stats_begin first");
-    if (eng->st_nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the flow statistics have no samples yet");
-  }
-  if (s.source == HNUMO_SAMPLE_VORT && !eng->vort_on)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the vorticity products, which need f: call hnumo_vort_begin first");
-  SampleArgs a{};
-  a.nstat = eng->nstat;
-  a.f = eng->vt_f;
-  a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
-  a.q = eng->q;
-  a.qb = eng->qb;
-  a.zbot = eng->nstat + (size_t)NS_ZB * eng->npoin;
-  a.alpha = eng->alpha;
-  a.sums = (const double2 *)eng->st_sums;
-  a.gravity = eng->p.gravity;
-  a.nsamp = (double)eng->st_nsamples;
-  a.chunk_pt = s.d_chunk_pt;
-  a.chunk_el = s.d_chunk_el;
-  a.el_list = s.d_el_list;
-  a.slot = s.d_slot;
-  a.perm = s.d_perm;
-  a.w = s.d_w;
-  a.out = dst;
-  a.npoin = (size_t)eng->npoin;
-  a.M = (size_t)s.plan.M;
-  if (s.source == HNUMO_SAMPLE_VORT)
-    sample_launch_ngl<SP_SRC_VORT>(eng, s.plan.nchunks(), a);
-  else if (s.source == HNUMO_SAMPLE_STATS)
-    sample_launch_ngl<SP_SRC_STATS>(eng, s.plan.nchunks(), a);
-  else
-    sample_launch_ngl<SP_SRC_STATE>(eng, s.plan.nchunks(), a);
-  HIPCHK(hipGetLastError());
-  return HNUMO_OK;
-}
-
-// planar [V][M] entries -> the caller's (V,M[,count])
-static void sample_transpose(const double *raw, int V, size_t M, size_t count, double *out) {
-  for (size_t c = 0; c < count; c++)
-    for (int v = 0; v < V; v++) {
-      const double *r = raw + (c * V + v) * M;
-      double *o = out + c * V * M + v;
-      for (size_t m = 0; m < M; m++) o[m * V] = r[m];
-    }
-}
-
-int hnumo_sample(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = sample_set(eng, id, "hnumo_sample");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: out is NULL");
-  const int64_t want = (int64_t)s->V * s->plan.M;
-  if (n != want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: n must be V*M = " + std::to_string(want) + ", got " + std::to_string(n));
-  HIPCHK(hipSetDevice(eng->device));
-  if (int rc = sample_now(eng, *s, s->d_out, "hnumo_sample")) return rc;
-  std::vector<double> raw((size_t)want);
-  HIPCHK(hipMemcpyAsync(raw.data(), s->d_out, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  sample_transpose(raw.data(), s->V, (size_t)s->plan.M, 1, out);
-  return HNUMO_OK;
-}
-
-int hnumo_sample_series_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = sample_set(eng, id, "hnumo_sample_series_begin");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (every < 0 || capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_series_begin: every and capacity must be >= 0, got " +
-                                            std::to_string(every) + ", " + std::to_string(capacity));
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a recording in flight writes the old series)
-  if (s->d_series) (void)hipFree(s->d_series);
-  s->d_series = nullptr;
-  s->every = s->cap = s->count = 0;
-  s->steps = 0;
-  if (capacity == 0) return HNUMO_OK;       // (no series: nothing to record into)
-  if (hipMalloc((void **)&s->d_series, (size_t)capacity * s->V * (size_t)s->plan.M * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    s->d_series = nullptr;
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_sample_series_begin: device allocation failed");
-  }
-  s->every = every;
-  s->cap = capacity;
-  return HNUMO_OK;
-}
-
-static int sample_record(hnumo_engine *eng, hnumo_engine::SampleSet &s, int id, const char *who) {
-  if (s.count >= s.cap)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series of sample set " + std::to_string(id) + " is full (" +
-                                            std::to_string(s.cap) + " samples): nothing recorded; read it with clear = 1");
-  if (int rc = sample_now(eng, s, s.d_series + (size_t)s.count * s.V * (size_t)s.plan.M, who)) return rc;
-  s.count++;
-  return HNUMO_OK;
-}
-
-static int sample_after_step(hnumo_engine *eng) {
-  int rc = 0;
-  for (int id = 0; id < SP_MAXSETS; id++) {
-    auto &s = eng->samples[id];
-    if (!s.used || s.every <= 0) continue;
-    if (++s.steps % s.every) continue;
-    const int r = sample_record(eng, s, id, "sample series after the step (the step itself succeeded)");
-    if (!rc) rc = r;
-  }
-  return rc;
-}
-
-int hnumo_sample_record(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = sample_set(eng, id, "hnumo_sample_record");
-  if (!s) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  return sample_record(eng, *s, id, "hnumo_sample_record");
-}
-
-int hnumo_sample_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = sample_set(eng, id, "hnumo_sample_series");
-  if (!s) return HNUMO_ERR_INVALID;
-  const int64_t want = (int64_t)s->V * s->plan.M * s->count;
-  if (n < 0 || (out && n < want))
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_series: out holds n = " + std::to_string(n) +
-                                            " values, the series has V*M*count = " + std::to_string(want));
-  HIPCHK(hipSetDevice(eng->device));
-  if (out && want > 0) {
-    std::vector<double> raw((size_t)want);
-    HIPCHK(hipMemcpyAsync(raw.data(), s->d_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    HIPCHK(hipStreamSynchronize(eng->stream));
-    HIPCHK(hipGetLastError());
-    sample_transpose(raw.data(), s->V, (size_t)s->plan.M, (size_t)s->count, out);
-  }
-  if (count) *count = s->count;
-  // (the next recording's slot is written after this copy on the same stream)
-  if (clear && out) s->count = 0;
-  return HNUMO_OK;
-}
-
-int hnumo_sample_destroy(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!sample_set(eng, id, "hnumo_sample_destroy")) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the set's tables)
-  sample_free(eng, id);
-  return HNUMO_OK;
-}
-
-// ------------------------------------------------------------------ float sets
-// (kernels_float.hip, float_plan.h; plain launches on the engine stream, outside the captured step,
-// like the sample sets: the step's launches, graph and bits are the same with or without sets)
-static void floats_free(hnumo_engine *eng, int id) {
-  auto &s = eng->floats[id];
-  for (void *p : {(void *)s.d_geo, (void *)s.d_nbr, (void *)s.d_f, (void *)s.d_i, (void *)s.d_series})
-    if (p) (void)hipFree(p);
-  s = hnumo_engine::FloatSet{};
-}
-
-// the set `id` of the engine, or nullptr with the message set
-static hnumo_engine::FloatSet *floats_set(hnumo_engine *eng, int32_t id, const char *who) {
-  if (id < 0 || id >= FL_MAXSETS || !eng->floats[id].used) {
-    fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no float set with id " + std::to_string(id));
-    return nullptr;
-  }
-  return &eng->floats[id];
-}
-
-// the plan's floats (sorted order) to the device
-static bool floats_upload(hnumo_engine::FloatSet &s, const FloatPlan &pl) {
-  const size_t M = (size_t)pl.M;
-  bool ok = true;
-  const std::vector<double> *fd[6] = {&pl.x, &pl.y, &pl.wx, &pl.wy, &pl.xi, &pl.eta};
-  for (int v = 0; v < 6; v++) ok = ok && hipMemcpy(s.d_f + v * M, fd[v]->data(), M * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  const std::vector<int32_t> *id[5] = {&pl.elem, &pl.layer, &pl.status, &pl.fresh, &pl.perm};
-  for (int v = 0; v < 5; v++) ok = ok && hipMemcpy(s.d_i + v * M, id[v]->data(), M * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  return ok;
-}
-
-int hnumo_floats_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
-                        const int32_t *layer, int64_t M, int32_t *id) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  const char *who = "hnumo_floats_create";
-  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
-  if (eng->L < 1 || eng->L > MAXL || !float_ngl_ok(eng->ngl))
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
-  if (!eng->fl_nbr_err.empty()) return fail(eng, HNUMO_ERR_INVALID, eng->fl_nbr_err);
-  int slot = -1;
-  for (int i = 0; i < FL_MAXSETS && slot < 0; i++)
-    if (!eng->floats[i].used) slot = i;
-  if (slot < 0)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the engine holds " + std::to_string(FL_MAXSETS) +
-                                            " float sets already (hnumo_floats_destroy frees one)");
-  FloatGeom geom;
-  if (int rc = float_geometry(coord, ldc, xgl, eng->ngl, eng->nelem_owned, eng->fl_nbr, geom, eng->err)) return rc;
-  FloatPlan pl;
-  if (int rc = float_seed(geom, eng->L, xy, layer, M, pl, eng->err, who)) return rc;
-  HIPCHK(hipSetDevice(eng->device));
-  auto &s = eng->floats[slot];
-  s = hnumo_engine::FloatSet{};
-  const size_t ne = (size_t)geom.ne, m = (size_t)M;
-  bool ok = hipMalloc((void **)&s.d_geo, (9 * ne + 1) * sizeof(double)) == hipSuccess &&
-            hipMalloc((void **)&s.d_nbr, (4 * ne + 1) * sizeof(int)) == hipSuccess &&
-            hipMalloc((void **)&s.d_f, 6 * m * sizeof(double)) == hipSuccess &&
-            hipMalloc((void **)&s.d_i, 5 * m * sizeof(int)) == hipSuccess;
-  if (ok && ne > 0)
-    ok = hipMemcpy(s.d_geo, geom.corners.data(), 8 * ne * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(s.d_geo + 8 * ne, geom.tol.data(), ne * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(s.d_nbr, geom.nbr.data(), 4 * ne * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && floats_upload(s, pl);
-  if (!ok) {
-    (void)hipGetLastError();
-    floats_free(eng, slot);
-    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
-  }
-  s.M = M;
-  s.geom = std::move(geom);
-  s.perm = std::move(pl.perm);
-  s.used = true;
-  *id = slot;
-  return HNUMO_OK;
-}
-
-int hnumo_floats_set(hnumo_engine *eng, int32_t id, const double *xy, const int32_t *layer, int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_set");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_set: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
-  FloatPlan pl;
-  if (int rc = float_seed(s->geom, eng->L, xy, layer, M, pl, eng->err, "hnumo_floats_set")) return rc;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight writes the old floats)
-  if (!floats_upload(*s, pl)) {
-    (void)hipGetLastError();
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_set: upload failed");
-  }
-  s->perm = std::move(pl.perm);
-  return HNUMO_OK;
-}
-
-static FloatArgs floats_args(hnumo_engine *eng, const hnumo_engine::FloatSet &s) {
-  FloatArgs a{};
-  const size_t ne = (size_t)s.geom.ne, M = (size_t)s.M;
-  a.f.corners = s.d_geo;
-  a.f.tol = s.d_geo + 8 * ne;
-  a.f.nbr = s.d_nbr;
-  a.f.q = eng->q;
-  a.f.npoin = (size_t)eng->npoin;
-  for (int i = 0; i < s.geom.ngl; i++) a.f.xgl[i] = s.geom.xgl[i];
-  a.x = s.d_f, a.y = s.d_f + M, a.wx = s.d_f + 2 * M, a.wy = s.d_f + 3 * M, a.xi = s.d_f + 4 * M, a.eta = s.d_f + 5 * M;
-  a.elem = s.d_i, a.layer = s.d_i + M, a.status = s.d_i + 2 * M, a.fresh = s.d_i + 3 * M, a.perm = s.d_i + 4 * M;
-  a.M = M;
-  return a;
-}
-
-extern "C++" template <int NGL>
-static void floats_launch(hnumo_engine *eng, const FloatArgs &a) {
-  constexpr int G = fl_group(NGL);
-  if (eng->fl_rows)
-    hipLaunchKernelGGL((float_advance_kernel<NGL, G>), dim3((unsigned)((a.M * G + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
-                       eng->stream, a);
-  else
-    hipLaunchKernelGGL((float_advance_kernel<NGL, 1>), dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
-                       eng->stream, a);
-}
-
-// one record of the set into the series, ordered after what is on the engine stream
-static int floats_record(hnumo_engine *eng, hnumo_engine::FloatSet &s, int id, const char *who) {
-  if (s.count >= s.cap)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series of float set " + std::to_string(id) + " is full (" +
-                                            std::to_string(s.cap) + " records): nothing recorded; read it with clear = 1");
-  FloatArgs a = floats_args(eng, s);
-  a.rec = s.d_series + (size_t)s.count * FL_NREC * (size_t)s.M;
-  hipLaunchKernelGGL(float_record_kernel, dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0, eng->stream, a);
-  HIPCHK(hipGetLastError());
-  s.count++;
-  return HNUMO_OK;
-}
-
-// one advance of the set on the state on the device now, and the record that is due after it
-static int floats_advance(hnumo_engine *eng, hnumo_engine::FloatSet &s, int id, double dt, const char *who) {
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  if (!float_finite(dt)) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": dt is not finite");
-  FloatArgs a = floats_args(eng, s);
-  a.dt = dt;
-  switch (eng->ngl) {
-    case 3: floats_launch<3>(eng, a); break;
-    case 4: floats_launch<4>(eng, a); break;
-    case 5: floats_launch<5>(eng, a); break;
-    case 6: floats_launch<6>(eng, a); break;
-    default: floats_launch<8>(eng, a); break;
-  }
-  HIPCHK(hipGetLastError());
-  s.advances++;
-  if (s.rec_every > 0 && s.advances % s.rec_every == 0) return floats_record(eng, s, id, who);
-  return HNUMO_OK;
-}
-
-static int floats_after_step(hnumo_engine *eng) {
-  int rc = 0;
-  for (int id = 0; id < FL_MAXSETS; id++) {
-    auto &s = eng->floats[id];
-    if (!s.used || s.every != 1) continue;
-    const int r = floats_advance(eng, s, id, eng->p.dt, "float set after the step (the step itself succeeded)");
-    if (!rc) rc = r;
-  }
-  return rc;
-}
-
-int hnumo_floats_advance(hnumo_engine *eng, int32_t id, double dt) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_advance");
-  if (!s) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  return floats_advance(eng, *s, id, dt, "hnumo_floats_advance");
-}
-
-int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t record_every, int32_t capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_begin");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (every != 0 && every != 1)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: every must be 0 or 1 (a float cannot skip steps), got " + std::to_string(every));
-  if (record_every < 0 || capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: record_every and capacity must be >= 0, got " +
-                                            std::to_string(record_every) + ", " + std::to_string(capacity));
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a record in flight writes the old series)
-  if (s->d_series) (void)hipFree(s->d_series);
-  s->d_series = nullptr;
-  s->every = s->rec_every = s->cap = s->count = 0;
-  s->advances = 0;
-  if (capacity > 0 && hipMalloc((void **)&s->d_series, (size_t)capacity * FL_NREC * (size_t)s->M * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    s->d_series = nullptr;
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_begin: device allocation failed");
-  }
-  s->every = every;
-  s->rec_every = record_every;
-  s->cap = capacity;
-  return HNUMO_OK;
-}
-
-int hnumo_floats_record(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_record");
-  if (!s) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  return floats_record(eng, *s, id, "hnumo_floats_record");
-}
-
-int hnumo_floats_get(hnumo_engine *eng, int32_t id, double *x, double *y, double *u, double *v, int32_t *elem, int32_t *status,
-                     int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_get");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_get: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
-  HIPCHK(hipSetDevice(eng->device));
-  const size_t m = (size_t)M;
-  std::vector<double> fd(4 * m);
-  std::vector<int32_t> fi(3 * m);
-  HIPCHK(hipMemcpyAsync(fd.data(), s->d_f, 4 * m * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipMemcpyAsync(fi.data(), s->d_i, 3 * m * sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  double *od[4] = {x, y, u, v};
-  for (size_t t = 0; t < m; t++) {
-    const size_t p = (size_t)s->perm[t];
-    for (int c = 0; c < 4; c++)
-      if (od[c]) od[c][p] = fd[c * m + t];
-    if (elem) elem[p] = fi[t];
-    if (status) status[p] = fi[2 * m + t];
-  }
-  return HNUMO_OK;
-}
-
-int hnumo_floats_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_plan");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_plan: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
-  HIPCHK(hipSetDevice(eng->device));
-  const size_t m = (size_t)M;
-  std::vector<double> fd(2 * m);
-  std::vector<int32_t> fi(m);
-  HIPCHK(hipMemcpyAsync(fd.data(), s->d_f + 4 * m, 2 * m * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipMemcpyAsync(fi.data(), s->d_i, m * sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  for (size_t t = 0; t < m; t++) {
-    const size_t p = (size_t)s->perm[t];
-    if (elem) elem[p] = fi[t];
-    if (xi_eta) xi_eta[2 * p] = fd[t], xi_eta[2 * p + 1] = fd[m + t];
-  }
-  return HNUMO_OK;
-}
-
-int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_series");
-  if (!s) return HNUMO_ERR_INVALID;
-  const int64_t want = (int64_t)FL_NREC * s->M * s->count;
-  if (n < 0 || (out && n < want))
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_series: out holds n = " + std::to_string(n) +
-                                            " values, the series has 5*M*count = " + std::to_string(want));
-  HIPCHK(hipSetDevice(eng->device));
-  if (out && want > 0) {
-    std::vector<double> raw((size_t)want);
-    HIPCHK(hipMemcpyAsync(raw.data(), s->d_series, (size_t)want * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    HIPCHK(hipStreamSynchronize(eng->stream));
-    HIPCHK(hipGetLastError());
-    sample_transpose(raw.data(), FL_NREC, (size_t)s->M, (size_t)s->count, out);
-  }
-  if (count) *count = s->count;
-  if (clear && out) s->count = 0;
-  return HNUMO_OK;
-}
-
-int hnumo_floats_destroy(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!floats_set(eng, id, "hnumo_floats_destroy")) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight uses the set's tables)
-  floats_free(eng, id);
   return HNUMO_OK;
 }
 
@@ -3231,15 +2258,15 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
   for (auto &t : th) t.join();
   for (int i = 0; i < n; i++)
     if (rc[i]) return rc[i];
-  // (the step of every engine succeeded: the flow statistics' samples, each on its engine's stream)
+  // (the step of every engine succeeded: every engine's observers run, each on its engine's stream,
+  // whatever another one returns; the first non-zero code is returned)
+  int ro = 0;
   for (int i = 0; i < n; i++) {
     (void)hipSetDevice(engines[i]->device);
-    if (int r = stats_after_step(engines[i])) return r;
-    if (int r = vort_after_step(engines[i])) return r;
-    if (int r = sample_after_step(engines[i])) return r;
-    if (int r = floats_after_step(engines[i])) return r;
+    const int r = observers_after_step(engines[i]);
+    if (!ro) ro = r;
   }
-  return 0;
+  return ro;
 }
 
 // Per-kernel breakdown of a step: `nsteps` direct (uncaptured) steps of the resident device state

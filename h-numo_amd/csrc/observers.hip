@@ -1,0 +1,906 @@
+// observers.hip -- what runs after a successful step of the resident state: the online flow
+// statistics (kernels_stats.hip), the vorticity products (kernels_vort.hip), the sample sets
+// (kernels_sample.hip, sample_plan.h) and the float sets (kernels_float.hip, float_plan.h).
+//
+// Part of engine.hip's translation unit: included there once fail, HIPCHK and struct hnumo_engine
+// (with Series and TreeSum) are defined.  All of it is plain launches on the engine stream outside
+// the captured step: the step's launches, graph and bits are the same with or without observers.
+//
+// An observer is a kernel, a Series, an entry in observers_after_step and a free in
+// hnumo_engine_destroy; the pieces below are what the four have in common.
+
+// ------------------------------------------------------------------ shared pieces
+// eng->L and eng->ngl as compile-time constants for a generic lambda (unsupported values are
+// refused before any launch; the default arms are never taken for them)
+template <class F>
+static void with_L(int L, F &&f) {
+  switch (L) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
+  }
+}
+
+template <class F>
+static void with_ngl(int ngl, F &&f) {
+  switch (ngl) {
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
+
+static bool sample_ngl_ok(int ngl) { return ngl == 3 || ngl == 4 || ngl == 5 || ngl == 6 || ngl == 8; }
+
+// a copy back on the engine stream, waited for
+static int download(hnumo_engine *eng, void *host, const void *dev, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  return HNUMO_OK;
+}
+
+static bool alloc_doubles(double **p, size_t n) { return hipMalloc((void **)p, (n ? n : 1) * sizeof(double)) == hipSuccess; }
+
+// free these and null them
+template <class... T>
+static void dfree(T *&...p) {
+  ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
+}
+
+// the set `id` of sets[], or nullptr with the message set; the first unused slot of sets[], or -1
+template <class Set, int N>
+static Set *set_by_id(hnumo_engine *eng, Set (&sets)[N], int32_t id, const char *who, const char *kind) {
+  if (id < 0 || id >= N || !sets[id].used) {
+    fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no " + kind + " set with id " + std::to_string(id));
+    return nullptr;
+  }
+  return &sets[id];
+}
+
+template <class Set, int N>
+static int free_slot(const Set (&sets)[N]) {
+  for (int i = 0; i < N; i++)
+    if (!sets[i].used) return i;
+  return -1;
+}
+
+// ---- Series: a ring of `cap` entries of `width` doubles on the device.  every > 0: an entry is due
+// after every every-th of the events counted in steps (successful steps; a float set's advances)
+static void series_free(Series &s) {
+  dfree(s.d);
+  s = Series{};
+}
+
+// from empty again (the caller has drained the stream: a recording in flight writes the old ring)
+static hipError_t series_begin(hnumo_engine *eng, Series &s, size_t width, int every, int cap, bool zero) {
+  series_free(s);
+  s.width = width;
+  if (cap > 0) {
+    hipError_t err = hipMalloc((void **)&s.d, (size_t)cap * width * sizeof(double));
+    if (err == hipSuccess && zero) err = hipMemsetAsync(s.d, 0, (size_t)cap * width * sizeof(double), eng->stream);
+    if (err != hipSuccess) {
+      (void)hipGetLastError();
+      series_free(s);
+      return err;
+    }
+  }
+  s.every = every;
+  s.cap = cap;
+  return hipSuccess;
+}
+
+static bool series_due(Series &s) { return s.every > 0 && ++s.steps % s.every == 0; }
+
+static double *series_slot(const Series &s) { return s.d + (size_t)s.count * s.width; }
+
+// 0 while there is room, else the refusal: "<who>: <which> is full (<cap> <entries>): nothing <done>; ..."
+static int series_full(hnumo_engine *eng, const Series &s, const char *who, const std::string &which, const char *entries,
+                       const char *done) {
+  if (s.count < s.cap) return 0;
+  return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": " + which + " is full (" + std::to_string(s.cap) + " " + entries +
+                                          "): nothing " + done + "; read it with clear = 1");
+}
+
+// planar [V][M] entries -> the caller's (V,M[,count])
+static void sample_transpose(const double *raw, int V, size_t M, size_t count, double *out) {
+  for (size_t c = 0; c < count; c++)
+    for (int v = 0; v < V; v++) {
+      const double *r = raw + (c * V + v) * M;
+      double *o = out + c * V * M + v;
+      for (size_t m = 0; m < M; m++) o[m * V] = r[m];
+    }
+}
+
+// the entries held into `out` (NULL: the count alone), as they are (V = 0) or each from planar [V][M]
+// to (V,M); `shape`: the entry's width in the caller's words
+static int series_read(hnumo_engine *eng, Series &s, int V, size_t M, double *out, int64_t n, int64_t *count, int32_t clear,
+                       const char *who, const char *shape) {
+  const int64_t want = (int64_t)s.width * s.count;
+  if (n < 0 || (out && n < want))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": out holds n = " + std::to_string(n) +
+                                            " values, the series has " + shape + "*count = " + std::to_string(want));
+  HIPCHK(hipSetDevice(eng->device));
+  if (out && want > 0) {
+    std::vector<double> raw(V ? (size_t)want : 0);
+    if (int rc = download(eng, V ? raw.data() : out, s.d, (size_t)want * sizeof(double))) return rc;
+    if (V) sample_transpose(raw.data(), V, M, (size_t)s.count, out);
+  }
+  if (count) *count = s.count;
+  // (the next entry's slot is written after this copy on the same stream)
+  if (clear && out) s.count = 0;
+  return HNUMO_OK;
+}
+
+// ---- TreeSum: `rows` rows of per-element partials [rows][ne] summed pairwise over aligned chunks,
+// the same tree for any ne (kernels_stats.hip: stats_tree_kernel)
+static bool tree_alloc(TreeSum &t, int rows, int ne) {
+  const size_t nch = ((size_t)ne + ST_CHUNK - 1) / ST_CHUNK;
+  return alloc_doubles(&t.part, (size_t)rows * ne) && alloc_doubles(&t.tree[0], rows * nch) &&
+         alloc_doubles(&t.tree[1], rows * ((nch + ST_CHUNK - 1) / ST_CHUNK));
+}
+
+static void tree_free(TreeSum &t) { dfree(t.part, t.tree[0], t.tree[1]); }
+
+// passes over aligned chunks until one value per row is left, which the last pass writes to dst[rows]
+static void tree_sum(hnumo_engine *eng, const TreeSum &t, int rows, int ne, double *dst) {
+  const double *in = t.part;
+  int n = ne, pass = 0;
+  for (;;) {
+    const int nch = (n + ST_CHUNK - 1) / ST_CHUNK;
+    const bool last = nch == 1;
+    double *out = last ? dst : t.tree[pass & 1];
+    hipLaunchKernelGGL(stats_tree_kernel, dim3(nch, rows), dim3(ST_BS), 0, eng->stream, in, n, out, last ? 1 : nch);
+    if (last) break;
+    in = out;
+    n = nch;
+    pass++;
+  }
+}
+
+// ------------------------------------------------------------------ online flow statistics
+// eng->stats: the running sums [L][2][npoin] pairs, the element partials [2L][ne] and their tree, the
+// series [capacity][L][2]; nsamples: samples taken since begin
+static void stats_free(hnumo_engine *eng) {
+  auto &st = eng->stats;
+  dfree(st.sums);
+  tree_free(st.tree);
+  series_free(st.series);
+  st.on = false;
+  st.nsamples = 0;
+}
+
+static size_t stats_nsums(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
+
+extern "C" int hnumo_stats_begin(hnumo_engine *eng, int32_t every, int32_t series_capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (every < 0 || series_capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: every and series_capacity must be >= 0, got " +
+                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  if (eng->L < 1 || eng->L > MAXL || eng->ngl < 2 || eng->ngl * eng->ngl > ST_BS)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: unsupported nlayers or ngl");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
+  stats_free(eng);
+  auto &st = eng->stats;
+  const int rows = 2 * eng->L;
+  if (!alloc_doubles(&st.sums, stats_nsums(eng)) || (series_capacity > 0 && !tree_alloc(st.tree, rows, eng->nelem_owned)) ||
+      series_begin(eng, st.series, rows, every, series_capacity, true) != hipSuccess) {
+    stats_free(eng);
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_stats_begin: device allocation failed");
+  }
+  HIPCHK(hipMemsetAsync(st.sums, 0, stats_nsums(eng) * sizeof(double), eng->stream));
+  st.on = true;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_stats_end(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats.on) return HNUMO_OK;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  stats_free(eng);
+  return HNUMO_OK;
+}
+
+// one sample of the state on the device, ordered after what is on the engine stream; no copy back
+static int stats_sample(hnumo_engine *eng, const char *who) {
+  auto &st = eng->stats;
+  if (!st.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_stats_begin first");
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  const bool series = st.series.cap > 0;
+  if (series)
+    if (int rc = series_full(eng, st.series, who, "the series", "samples", "accumulated")) return rc;
+  const int ne = eng->nelem_owned, EPB = ST_BS / eng->P;
+  if (ne > 0) {
+    StatsArgs a{};
+    a.q = eng->q;
+    a.alpha = eng->alpha;
+    a.w = eng->nstat + (size_t)NS_W * eng->npoin;
+    a.sums = (double2 *)st.sums;
+    a.part = st.tree.part;
+    a.gravity = eng->p.gravity;
+    a.npoin = eng->npoin;
+    a.ne = ne;
+    a.ngl = eng->ngl;
+    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    with_L(eng->L, [&](auto l) {
+      constexpr int L = decltype(l)::value;
+      if (series)
+        hipLaunchKernelGGL((stats_accumulate_kernel<L, true>), dim3(nb), dim3(ST_BS), 0, eng->stream, a);
+      else
+        hipLaunchKernelGGL((stats_accumulate_kernel<L, false>), dim3(nb), dim3(ST_BS), 0, eng->stream, a);
+    });
+    if (series) tree_sum(eng, st.tree, 2 * eng->L, ne, series_slot(st.series));
+    HIPCHK(hipGetLastError());
+  }
+  if (series) st.series.count++;
+  st.nsamples++;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_stats_accumulate(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return stats_sample(eng, "hnumo_stats_accumulate");
+}
+
+// the sums between the device layout [L][2][npoin][2] and the caller's (4,npoin,L)
+extern "C" int hnumo_stats_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: call hnumo_stats_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: out is NULL");
+  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  if (int rc = download(eng, raw.data(), eng->stats.sums, want * sizeof(double))) return rc;
+  for (int k = 0; k < eng->L; k++)
+    for (int p = 0; p < 2; p++)
+      for (size_t I = 0; I < npoin; I++)
+        for (int j = 0; j < 2; j++) out[4 * (I + npoin * k) + 2 * p + j] = raw[2 * st_pair(k, p, I, npoin) + j];
+  if (nsamples) *nsamples = eng->stats.nsamples;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_stats_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: call hnumo_stats_begin first");
+  if (!in) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: in is NULL");
+  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: nsamples must be >= 0");
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  for (int k = 0; k < eng->L; k++)
+    for (int p = 0; p < 2; p++)
+      for (size_t I = 0; I < npoin; I++)
+        for (int j = 0; j < 2; j++) raw[2 * st_pair(k, p, I, npoin) + j] = in[4 * (I + npoin * k) + 2 * p + j];
+  HIPCHK(hipMemcpyAsync(eng->stats.sums, raw.data(), want * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  eng->stats.nsamples = nsamples;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_stats_fields(hnumo_engine *eng, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: call hnumo_stats_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: out is NULL");
+  const int64_t want = 5 * (int64_t)eng->npoin * eng->L;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: n must be 5*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  if (eng->stats.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: no samples yet");
+  HIPCHK(hipSetDevice(eng->device));
+  double *d = nullptr;
+  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
+  const size_t npoin = (size_t)eng->npoin, nown = (size_t)eng->nelem_owned * eng->P;
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((npoin + ST_BS - 1) / ST_BS, 4096));
+  const double2 *s = (const double2 *)eng->stats.sums;
+  const double ns = (double)eng->stats.nsamples;
+  with_L(eng->L, [&](auto l) {
+    hipLaunchKernelGGL(stats_fields_kernel<decltype(l)::value>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d);
+  });
+  const int rc = download(eng, out, d, (size_t)want * sizeof(double));
+  (void)hipFree(d);
+  return rc;
+}
+
+extern "C" int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_series: call hnumo_stats_begin first");
+  return series_read(eng, eng->stats.series, 0, 0, out, n, count, clear, "hnumo_stats_series", "2*nlayers");
+}
+
+// ------------------------------------------------------------------ vorticity products
+// eng->vort: the caller's coriolis_df (NULL: f = 0), the fields of the last sample planar
+// [L][4][npoin], the element partials [3L][ne] and their tree, the series [capacity][L][3]
+static void vort_free(hnumo_engine *eng) {
+  auto &vt = eng->vort;
+  dfree(vt.f, vt.fields);
+  tree_free(vt.tree);
+  series_free(vt.series);
+  vt.on = false;
+}
+
+static size_t vort_nfields(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
+
+extern "C" int hnumo_vort_begin(hnumo_engine *eng, const double *coriolis_df, int32_t every, int32_t series_capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (every < 0 || series_capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: every and series_capacity must be >= 0, got " +
+                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: unsupported nlayers or ngl");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
+  vort_free(eng);
+  auto &vt = eng->vort;
+  const int rows = 3 * eng->L;
+  bool ok = alloc_doubles(&vt.fields, vort_nfields(eng)) && (!coriolis_df || alloc_doubles(&vt.f, (size_t)eng->npoin)) &&
+            (series_capacity == 0 || tree_alloc(vt.tree, rows, eng->nelem_owned)) &&
+            series_begin(eng, vt.series, rows, every, series_capacity, true) == hipSuccess;
+  if (ok && coriolis_df)
+    ok = hipMemcpy(vt.f, coriolis_df, (size_t)eng->npoin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    vort_free(eng);
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_vort_begin: device allocation or upload failed");
+  }
+  // (the nodes of ghost elements are never written: they read 0)
+  HIPCHK(hipMemsetAsync(vt.fields, 0, vort_nfields(eng) * sizeof(double), eng->stream));
+  vt.on = true;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_vort_end(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->vort.on) return HNUMO_OK;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  vort_free(eng);
+  return HNUMO_OK;
+}
+
+// the fields of the state on the device into vort.fields, with `series` the next series entry too;
+// ordered after what is on the engine stream, no copy back
+static int vort_form(hnumo_engine *eng, bool series, const char *who) {
+  auto &vt = eng->vort;
+  if (!vt.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_vort_begin first");
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (series && vt.series.cap == 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no series (hnumo_vort_begin with series_capacity = 0)");
+  if (series)
+    if (int rc = series_full(eng, vt.series, who, "the series", "samples", "recorded")) return rc;
+  const int ne = eng->nelem_owned, EPB = VT_BS / eng->P;
+  if (ne > 0) {
+    VortArgs a{};
+    a.q = eng->q;
+    a.alpha = eng->alpha;
+    a.nstat = eng->nstat;
+    a.f = vt.f;
+    a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
+    a.out = vt.fields;
+    a.part = vt.tree.part;
+    a.gravity = eng->p.gravity;
+    a.npoin = eng->npoin;
+    a.ne = ne;
+    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    with_ngl(eng->ngl, [&](auto ngl) {
+      with_L(eng->L, [&](auto l) {
+        constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
+        if (series)
+          hipLaunchKernelGGL((vort_kernel<NGL, L, true>), dim3(nb), dim3(VT_BS), 0, eng->stream, a);
+        else
+          hipLaunchKernelGGL((vort_kernel<NGL, L, false>), dim3(nb), dim3(VT_BS), 0, eng->stream, a);
+      });
+    });
+    if (series) tree_sum(eng, vt.tree, 3 * eng->L, ne, series_slot(vt.series));
+    HIPCHK(hipGetLastError());
+  }
+  if (series) vt.series.count++;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_vort_record(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return vort_form(eng, true, "hnumo_vort_record");
+}
+
+extern "C" int hnumo_vort_fields(hnumo_engine *eng, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->vort.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: call hnumo_vort_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: out is NULL");
+  const size_t want = vort_nfields(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: n must be 4*npoin*nlayers = " + std::to_string(want) +
+                                            ", got " + std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  if (int rc = vort_form(eng, false, "hnumo_vort_fields")) return rc;
+  std::vector<double> raw(want);
+  if (int rc = download(eng, raw.data(), eng->vort.fields, want * sizeof(double))) return rc;
+  // planar [L][4][npoin] -> the caller's (4,npoin,L)
+  for (int k = 0; k < eng->L; k++) sample_transpose(raw.data() + 4 * npoin * k, 4, npoin, 1, out + 4 * npoin * k);
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_vort_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->vort.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_series: call hnumo_vort_begin first");
+  return series_read(eng, eng->vort.series, 0, 0, out, n, count, clear, "hnumo_vort_series", "3*nlayers");
+}
+
+// ------------------------------------------------------------------ sample sets
+// eng->samples[]: the host plan (sample_plan.h), its tables on the device, one sample's output [V][M]
+// and the series [capacity][V][M]
+using SampleSet = hnumo_engine::SampleSet;
+
+static void sample_free(hnumo_engine *eng, int id) {
+  auto &s = eng->samples[id];
+  dfree(s.d_tab, s.d_w, s.d_out);
+  series_free(s.series);
+  s = SampleSet{};
+}
+
+static SampleSet *sample_set(hnumo_engine *eng, int32_t id, const char *who) {
+  return set_by_id(eng, eng->samples, id, who, "sample");
+}
+
+// the located or given points of `pl` become a set: tables built and uploaded
+static int sample_adopt(hnumo_engine *eng, SamplePlan &pl, const double *xgl, int32_t source, int32_t *id, const char *who) {
+  const int slot = free_slot(eng->samples);
+  if (slot < 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the engine holds " + std::to_string(SP_MAXSETS) +
+                                            " sample sets already (hnumo_sample_destroy frees one)");
+  const int V = sp_nval(eng->L, source);
+  sample_chunks(xgl, sp_K(eng->ngl, V), pl);
+  HIPCHK(hipSetDevice(eng->device));
+  auto &s = eng->samples[slot];
+  s = SampleSet{};
+  const size_t M = (size_t)pl.M, nch = (size_t)pl.nchunks(), nel = pl.el_list.size();
+  const size_t ntab = 2 * (nch + 1) + nel + 2 * M;
+  std::vector<int> tab;
+  tab.reserve(ntab);
+  for (const std::vector<int32_t> *v : {&pl.chunk_pt, &pl.chunk_el, &pl.el_list, &pl.slot, &pl.perm})
+    tab.insert(tab.end(), v->begin(), v->end());
+  bool ok = hipMalloc((void **)&s.d_tab, ntab * sizeof(int)) == hipSuccess &&
+            hipMalloc((void **)&s.d_w, pl.w.size() * sizeof(double)) == hipSuccess &&
+            hipMalloc((void **)&s.d_out, (size_t)V * M * sizeof(double)) == hipSuccess;
+  ok = ok && hipMemcpy(s.d_tab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(s.d_w, pl.w.data(), pl.w.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    sample_free(eng, slot);
+    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
+  }
+  s.d_chunk_pt = s.d_tab;
+  s.d_chunk_el = s.d_chunk_pt + nch + 1;
+  s.d_el_list = s.d_chunk_el + nch + 1;
+  s.d_slot = s.d_el_list + nel;
+  s.d_perm = s.d_slot + M;
+  s.source = source;
+  s.V = V;
+  s.plan = std::move(pl);
+  s.plan.w = std::vector<double>();   // (the device holds the weights and the work lists)
+  s.plan.slot = s.plan.perm = std::vector<int32_t>();
+  s.used = true;
+  *id = slot;
+  return HNUMO_OK;
+}
+
+static int sample_create_checks(hnumo_engine *eng, int32_t source, const int32_t *id, const char *who) {
+  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
+  if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS && source != HNUMO_SAMPLE_VORT)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS or " +
+                                            "HNUMO_SAMPLE_VORT, got " + std::to_string(source));
+  if (source == HNUMO_SAMPLE_VORT && !eng->vort.on)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": a set on the vorticity products needs f: call hnumo_vort_begin first");
+  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
+  return 0;
+}
+
+extern "C" int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
+                                   int64_t M, int32_t source, int32_t *id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create")) return rc;
+  SamplePlan pl;
+  if (int rc = sample_locate(coord, ldc, xgl, eng->ngl, eng->nelem_owned, xy, M, pl, eng->err)) return rc;
+  return sample_adopt(eng, pl, xgl, source, id, "hnumo_sample_create");
+}
+
+extern "C" int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, const int32_t *elem, const double *xi_eta,
+                                       int64_t M, int32_t source, int32_t *id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create_ref")) return rc;
+  SamplePlan pl;
+  if (int rc = sample_take_ref(xgl, eng->ngl, eng->nelem_owned, elem, xi_eta, M, pl, eng->err)) return rc;
+  return sample_adopt(eng, pl, xgl, source, id, "hnumo_sample_create_ref");
+}
+
+extern "C" int hnumo_sample_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const auto *s = sample_set(eng, id, "hnumo_sample_plan");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->plan.M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_plan: M must be the set's " + std::to_string(s->plan.M) + ", got " +
+                                            std::to_string(M));
+  if (elem) std::memcpy(elem, s->plan.elem.data(), (size_t)M * sizeof(int32_t));
+  if (xi_eta) std::memcpy(xi_eta, s->plan.xi_eta.data(), 2 * (size_t)M * sizeof(double));
+  return HNUMO_OK;
+}
+
+// one sample of the set into `dst` [V][M] on the device, ordered after what is on the engine stream
+static int sample_now(hnumo_engine *eng, const SampleSet &s, double *dst, const char *who) {
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (s.source == HNUMO_SAMPLE_STATS) {
+    if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the flow statistics: call hnumo_stats_begin first");
+    if (eng->stats.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the flow statistics have no samples yet");
+  }
+  if (s.source == HNUMO_SAMPLE_VORT && !eng->vort.on)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the vorticity products, which need f: call hnumo_vort_begin first");
+  SampleArgs a{};
+  a.nstat = eng->nstat;
+  a.f = eng->vort.f;
+  a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
+  a.q = eng->q;
+  a.qb = eng->qb;
+  a.zbot = eng->nstat + (size_t)NS_ZB * eng->npoin;
+  a.alpha = eng->alpha;
+  a.sums = (const double2 *)eng->stats.sums;
+  a.gravity = eng->p.gravity;
+  a.nsamp = (double)eng->stats.nsamples;
+  a.chunk_pt = s.d_chunk_pt;
+  a.chunk_el = s.d_chunk_el;
+  a.el_list = s.d_el_list;
+  a.slot = s.d_slot;
+  a.perm = s.d_perm;
+  a.w = s.d_w;
+  a.out = dst;
+  a.npoin = (size_t)eng->npoin;
+  a.M = (size_t)s.plan.M;
+  const int nch = s.plan.nchunks();
+  with_ngl(eng->ngl, [&](auto ngl) {
+    with_L(eng->L, [&](auto l) {
+      constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
+      if (s.source == HNUMO_SAMPLE_VORT)
+        hipLaunchKernelGGL((sample_kernel<NGL, L, SP_SRC_VORT>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a);
+      else if (s.source == HNUMO_SAMPLE_STATS)
+        hipLaunchKernelGGL((sample_kernel<NGL, L, SP_SRC_STATS>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a);
+      else
+        hipLaunchKernelGGL((sample_kernel<NGL, L, SP_SRC_STATE>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a);
+    });
+  });
+  HIPCHK(hipGetLastError());
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_sample(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: out is NULL");
+  const int64_t want = (int64_t)s->V * s->plan.M;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: n must be V*M = " + std::to_string(want) + ", got " + std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  if (int rc = sample_now(eng, *s, s->d_out, "hnumo_sample")) return rc;
+  std::vector<double> raw((size_t)want);
+  if (int rc = download(eng, raw.data(), s->d_out, (size_t)want * sizeof(double))) return rc;
+  sample_transpose(raw.data(), s->V, (size_t)s->plan.M, 1, out);
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_sample_series_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample_series_begin");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (every < 0 || capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_series_begin: every and capacity must be >= 0, got " +
+                                            std::to_string(every) + ", " + std::to_string(capacity));
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a recording in flight writes the old series)
+  // (no series: nothing to record into, so nothing is due after a step either)
+  if (series_begin(eng, s->series, (size_t)s->V * (size_t)s->plan.M, capacity ? every : 0, capacity, false) != hipSuccess)
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_sample_series_begin: device allocation failed");
+  return HNUMO_OK;
+}
+
+static int sample_record(hnumo_engine *eng, SampleSet &s, int id, const char *who) {
+  if (int rc = series_full(eng, s.series, who, "the series of sample set " + std::to_string(id), "samples", "recorded")) return rc;
+  if (int rc = sample_now(eng, s, series_slot(s.series), who)) return rc;
+  s.series.count++;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_sample_record(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample_record");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return sample_record(eng, *s, id, "hnumo_sample_record");
+}
+
+extern "C" int hnumo_sample_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = sample_set(eng, id, "hnumo_sample_series");
+  if (!s) return HNUMO_ERR_INVALID;
+  return series_read(eng, s->series, s->V, (size_t)s->plan.M, out, n, count, clear, "hnumo_sample_series", "V*M");
+}
+
+extern "C" int hnumo_sample_destroy(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!sample_set(eng, id, "hnumo_sample_destroy")) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the set's tables)
+  sample_free(eng, id);
+  return HNUMO_OK;
+}
+
+// ------------------------------------------------------------------ float sets
+// eng->floats[]: the host geometry (float_plan.h; hnumo_floats_set locates in it), the permutation
+// back to input order, the element tables and the SoA floats on the device, the series
+// [capacity][5][M].  The floats' own rules sit on top of the Series: `every` (0 or 1) is whether the
+// engine advances the set after a step; the series counts advances, not steps, and its every is the
+// caller's record_every
+using FloatSet = hnumo_engine::FloatSet;
+
+static void floats_free(hnumo_engine *eng, int id) {
+  auto &s = eng->floats[id];
+  dfree(s.d_geo, s.d_nbr, s.d_f, s.d_i);
+  series_free(s.series);
+  s = FloatSet{};
+}
+
+static FloatSet *floats_set(hnumo_engine *eng, int32_t id, const char *who) {
+  return set_by_id(eng, eng->floats, id, who, "float");
+}
+
+// the plan's floats (sorted order) to the device
+static bool floats_upload(FloatSet &s, const FloatPlan &pl) {
+  const size_t M = (size_t)pl.M;
+  bool ok = true;
+  const std::vector<double> *fd[6] = {&pl.x, &pl.y, &pl.wx, &pl.wy, &pl.xi, &pl.eta};
+  for (int v = 0; v < 6; v++) ok = ok && hipMemcpy(s.d_f + v * M, fd[v]->data(), M * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  const std::vector<int32_t> *id[5] = {&pl.elem, &pl.layer, &pl.status, &pl.fresh, &pl.perm};
+  for (int v = 0; v < 5; v++) ok = ok && hipMemcpy(s.d_i + v * M, id[v]->data(), M * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  return ok;
+}
+
+extern "C" int hnumo_floats_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
+                                   const int32_t *layer, int64_t M, int32_t *id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_floats_create";
+  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
+  if (eng->L < 1 || eng->L > MAXL || !float_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
+  if (!eng->fl_nbr_err.empty()) return fail(eng, HNUMO_ERR_INVALID, eng->fl_nbr_err);
+  const int slot = free_slot(eng->floats);
+  if (slot < 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the engine holds " + std::to_string(FL_MAXSETS) +
+                                            " float sets already (hnumo_floats_destroy frees one)");
+  FloatGeom geom;
+  if (int rc = float_geometry(coord, ldc, xgl, eng->ngl, eng->nelem_owned, eng->fl_nbr, geom, eng->err)) return rc;
+  FloatPlan pl;
+  if (int rc = float_seed(geom, eng->L, xy, layer, M, pl, eng->err, who)) return rc;
+  HIPCHK(hipSetDevice(eng->device));
+  auto &s = eng->floats[slot];
+  s = FloatSet{};
+  const size_t ne = (size_t)geom.ne, m = (size_t)M;
+  bool ok = hipMalloc((void **)&s.d_geo, (9 * ne + 1) * sizeof(double)) == hipSuccess &&
+            hipMalloc((void **)&s.d_nbr, (4 * ne + 1) * sizeof(int)) == hipSuccess &&
+            hipMalloc((void **)&s.d_f, 6 * m * sizeof(double)) == hipSuccess &&
+            hipMalloc((void **)&s.d_i, 5 * m * sizeof(int)) == hipSuccess;
+  if (ok && ne > 0)
+    ok = hipMemcpy(s.d_geo, geom.corners.data(), 8 * ne * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(s.d_geo + 8 * ne, geom.tol.data(), ne * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(s.d_nbr, geom.nbr.data(), 4 * ne * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && floats_upload(s, pl);
+  if (!ok) {
+    (void)hipGetLastError();
+    floats_free(eng, slot);
+    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
+  }
+  s.M = M;
+  s.geom = std::move(geom);
+  s.perm = std::move(pl.perm);
+  s.used = true;
+  *id = slot;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_set(hnumo_engine *eng, int32_t id, const double *xy, const int32_t *layer, int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_set");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_set: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  FloatPlan pl;
+  if (int rc = float_seed(s->geom, eng->L, xy, layer, M, pl, eng->err, "hnumo_floats_set")) return rc;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight writes the old floats)
+  if (!floats_upload(*s, pl)) {
+    (void)hipGetLastError();
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_set: upload failed");
+  }
+  s->perm = std::move(pl.perm);
+  return HNUMO_OK;
+}
+
+static FloatArgs floats_args(hnumo_engine *eng, const FloatSet &s) {
+  FloatArgs a{};
+  const size_t ne = (size_t)s.geom.ne, M = (size_t)s.M;
+  a.f.corners = s.d_geo;
+  a.f.tol = s.d_geo + 8 * ne;
+  a.f.nbr = s.d_nbr;
+  a.f.q = eng->q;
+  a.f.npoin = (size_t)eng->npoin;
+  for (int i = 0; i < s.geom.ngl; i++) a.f.xgl[i] = s.geom.xgl[i];
+  a.x = s.d_f, a.y = s.d_f + M, a.wx = s.d_f + 2 * M, a.wy = s.d_f + 3 * M, a.xi = s.d_f + 4 * M, a.eta = s.d_f + 5 * M;
+  a.elem = s.d_i, a.layer = s.d_i + M, a.status = s.d_i + 2 * M, a.fresh = s.d_i + 3 * M, a.perm = s.d_i + 4 * M;
+  a.M = M;
+  return a;
+}
+
+// one record of the set into the series, ordered after what is on the engine stream
+static int floats_record(hnumo_engine *eng, FloatSet &s, int id, const char *who) {
+  if (int rc = series_full(eng, s.series, who, "the series of float set " + std::to_string(id), "records", "recorded")) return rc;
+  FloatArgs a = floats_args(eng, s);
+  a.rec = series_slot(s.series);
+  hipLaunchKernelGGL(float_record_kernel, dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0, eng->stream, a);
+  HIPCHK(hipGetLastError());
+  s.series.count++;
+  return HNUMO_OK;
+}
+
+// one advance of the set on the state on the device now, and the record that is due after it
+static int floats_advance(hnumo_engine *eng, FloatSet &s, int id, double dt, const char *who) {
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (!float_finite(dt)) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": dt is not finite");
+  FloatArgs a = floats_args(eng, s);
+  a.dt = dt;
+  with_ngl(eng->ngl, [&](auto ngl) {
+    constexpr int NGL = decltype(ngl)::value, G = fl_group(NGL);
+    if (eng->fl_rows)
+      hipLaunchKernelGGL((float_advance_kernel<NGL, G>), dim3((unsigned)((a.M * G + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+                         eng->stream, a);
+    else
+      hipLaunchKernelGGL((float_advance_kernel<NGL, 1>), dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+                         eng->stream, a);
+  });
+  HIPCHK(hipGetLastError());
+  if (series_due(s.series)) return floats_record(eng, s, id, who);
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_advance(hnumo_engine *eng, int32_t id, double dt) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_advance");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return floats_advance(eng, *s, id, dt, "hnumo_floats_advance");
+}
+
+extern "C" int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t record_every, int32_t capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_begin");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (every != 0 && every != 1)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: every must be 0 or 1 (a float cannot skip steps), got " + std::to_string(every));
+  if (record_every < 0 || capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: record_every and capacity must be >= 0, got " +
+                                            std::to_string(record_every) + ", " + std::to_string(capacity));
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a record in flight writes the old series)
+  s->every = 0;
+  // (record_every holds with capacity 0 too: the record that falls due is then refused as into a full series)
+  if (series_begin(eng, s->series, FL_NREC * (size_t)s->M, record_every, capacity, false) != hipSuccess)
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_begin: device allocation failed");
+  s->every = every;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_record(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_record");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return floats_record(eng, *s, id, "hnumo_floats_record");
+}
+
+extern "C" int hnumo_floats_get(hnumo_engine *eng, int32_t id, double *x, double *y, double *u, double *v, int32_t *elem,
+                                int32_t *status, int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_get");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_get: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  HIPCHK(hipSetDevice(eng->device));
+  const size_t m = (size_t)M;
+  std::vector<double> fd(4 * m);
+  std::vector<int32_t> fi(3 * m);
+  if (int rc = download(eng, fd.data(), s->d_f, 4 * m * sizeof(double))) return rc;
+  if (int rc = download(eng, fi.data(), s->d_i, 3 * m * sizeof(int))) return rc;
+  double *od[4] = {x, y, u, v};
+  for (size_t t = 0; t < m; t++) {
+    const size_t p = (size_t)s->perm[t];
+    for (int c = 0; c < 4; c++)
+      if (od[c]) od[c][p] = fd[c * m + t];
+    if (elem) elem[p] = fi[t];
+    if (status) status[p] = fi[2 * m + t];
+  }
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_plan");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (M != s->M)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_plan: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  HIPCHK(hipSetDevice(eng->device));
+  const size_t m = (size_t)M;
+  std::vector<double> fd(2 * m);
+  std::vector<int32_t> fi(m);
+  if (int rc = download(eng, fd.data(), s->d_f + 4 * m, 2 * m * sizeof(double))) return rc;
+  if (int rc = download(eng, fi.data(), s->d_i, m * sizeof(int))) return rc;
+  for (size_t t = 0; t < m; t++) {
+    const size_t p = (size_t)s->perm[t];
+    if (elem) elem[p] = fi[t];
+    if (xi_eta) xi_eta[2 * p] = fd[t], xi_eta[2 * p + 1] = fd[m + t];
+  }
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_series");
+  if (!s) return HNUMO_ERR_INVALID;
+  return series_read(eng, s->series, FL_NREC, (size_t)s->M, out, n, count, clear, "hnumo_floats_series", "5*M");
+}
+
+extern "C" int hnumo_floats_destroy(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!floats_set(eng, id, "hnumo_floats_destroy")) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight uses the set's tables)
+  floats_free(eng, id);
+  return HNUMO_OK;
+}
+
+// ------------------------------------------------------------------ after a successful step
+// Called once run_steps has returned 0 (so a step redone on per-stage launches is observed once), in
+// this order: the statistics' sample; the vorticity series' sample; the sample sets' recordings, which
+// see the new sums of a set on the statistics; the float sets' advance by params.dt, last.  Every
+// observer runs whatever the others return (a float cannot skip a step because a series was full);
+// the first non-zero code is returned.
+static int observers_after_step(hnumo_engine *eng) {
+  int rc = 0;
+  auto run = [&](int r) {
+    if (!rc) rc = r;
+  };
+  if (eng->stats.on && series_due(eng->stats.series))
+    run(stats_sample(eng, "flow statistics after the step (the step itself succeeded)"));
+  if (eng->vort.on && eng->vort.series.cap > 0 && series_due(eng->vort.series))
+    run(vort_form(eng, true, "vorticity series after the step (the step itself succeeded)"));
+  for (int id = 0; id < SP_MAXSETS; id++) {
+    auto &s = eng->samples[id];
+    if (s.used && series_due(s.series)) run(sample_record(eng, s, id, "sample series after the step (the step itself succeeded)"));
+  }
+  for (int id = 0; id < FL_MAXSETS; id++) {
+    auto &s = eng->floats[id];
+    if (s.used && s.every == 1) run(floats_advance(eng, s, id, eng->p.dt, "float set after the step (the step itself succeeded)"));
+  }
+  return rc;
+}

@@ -304,6 +304,45 @@ class Engine:
         self._check(lib().hnumo_layer_fields(self.h, _dp(out), out.size))
         return out
 
+    # ---- what the observers below share
+    def _series(self, fn, head_shape, *ids, clear=False):
+        """(*head_shape, count) of a series: the (NULL, 0) query for the count, then the read."""
+        n = C.c_int64()
+        self._check(fn(self.h, *ids, None, 0, C.byref(n), 0))
+        out = np.zeros((*head_shape, n.value), order="F")
+        if n.value or clear:
+            buf = out if out.size else np.zeros(1)
+            self._check(fn(self.h, *ids, _dp(buf), out.size, C.byref(n), int(clear)))
+        return out
+
+    def _plan(self, fn, sid: int, M: int):
+        elem = np.zeros(M, dtype=np.int32)
+        xe = np.zeros((2, M), order="F")
+        self._check(fn(self.h, int(sid), elem.ctypes.data_as(C.POINTER(C.c_int32)), _dp(xe), M))
+        return elem, xe
+
+    def _coord_arg(self, coord):
+        coord = np.asfortranarray(coord, dtype=np.float64)
+        if coord.ndim != 2 or coord.shape[1] != self.dims["npoin"]:
+            raise ValueError(f"coord: shape {coord.shape}, expected (2 or 3, {self.dims['npoin']})")
+        return coord
+
+    @staticmethod
+    def _xy_arg(xy):
+        xy = np.asfortranarray(xy, dtype=np.float64)
+        if xy.ndim != 2 or xy.shape[0] != 2:
+            raise ValueError(f"xy: shape {xy.shape}, expected (2, M)")
+        return xy
+
+    def _sets(self, kind: str) -> dict:
+        """id -> sizes of the `kind` ("sample": (M, V); "float": M) sets created through this object."""
+        return self.__dict__.setdefault("_sets_", {}).setdefault(kind, {})
+
+    def _set_sizes(self, kind: str, sid: int):
+        if sid not in self._sets(kind):
+            raise EngineError(4, f"no {kind} set with id {sid}")
+        return self._sets(kind)[sid]
+
     # ---- online flow statistics on the device state (hnumo_stats_*; mirror: hnumo/flowstats.py)
     def stats_begin(self, every: int = 0, series: int = 0):
         """Allocate and zero the running sums (again: reset).  every = k >= 1: the engine samples
@@ -335,13 +374,7 @@ class Engine:
 
     def stats_series(self, clear: bool = False):
         """(2, nlayers, count) = (KE_k, VOL_k) per sample; clear empties the series afterwards."""
-        n = C.c_int64()
-        self._check(lib().hnumo_stats_series(self.h, None, 0, C.byref(n), 0))
-        out = np.zeros((2, self.dims["nlayers"], n.value), order="F")
-        if n.value or clear:
-            buf = out if out.size else np.zeros(1)
-            self._check(lib().hnumo_stats_series(self.h, _dp(buf), out.size, C.byref(n), int(clear)))
-        return out
+        return self._series(lib().hnumo_stats_series, (2, self.dims["nlayers"]), clear=clear)
 
     def stats_end(self):
         self._check(lib().hnumo_stats_end(self.h))
@@ -371,13 +404,7 @@ class Engine:
 
     def vort_series(self, clear: bool = False):
         """(3, nlayers, count) = (Z_k, PZ_k, G_k) per sample; clear empties the series afterwards."""
-        n = C.c_int64()
-        self._check(lib().hnumo_vort_series(self.h, None, 0, C.byref(n), 0))
-        out = np.zeros((3, self.dims["nlayers"], n.value), order="F")
-        if n.value or clear:
-            buf = out if out.size else np.zeros(1)
-            self._check(lib().hnumo_vort_series(self.h, _dp(buf), out.size, C.byref(n), int(clear)))
-        return out
+        return self._series(lib().hnumo_vort_series, (3, self.dims["nlayers"]), clear=clear)
 
     def vort_end(self):
         self._check(lib().hnumo_vort_end(self.h))
@@ -390,18 +417,12 @@ class Engine:
     def sample_create(self, coord, xgl, xy, source: int = 0) -> int:
         """A set from physical points xy (2, M), located in the owned elements from coord
         (2 or 3, npoin) and the LGL nodes xgl; source: SAMPLE_STATE or SAMPLE_STATS.  Returns its id."""
-        coord = np.asfortranarray(coord, dtype=np.float64)
-        if coord.ndim != 2 or coord.shape[1] != self.dims["npoin"]:
-            raise ValueError(f"coord: shape {coord.shape}, expected (2 or 3, {self.dims['npoin']})")
-        xgl = self._sample_xgl(xgl)
-        xy = np.asfortranarray(xy, dtype=np.float64)
-        if xy.ndim != 2 or xy.shape[0] != 2:
-            raise ValueError(f"xy: shape {xy.shape}, expected (2, M)")
+        coord, xgl, xy = self._coord_arg(coord), self._sample_xgl(xgl), self._xy_arg(xy)
         sid = C.c_int32(-1)
         dp = C.POINTER(C.c_double)
         self._check(lib().hnumo_sample_create(self.h, coord.ctypes.data_as(dp), coord.shape[0], xgl.ctypes.data_as(dp),
                                               xy.ctypes.data_as(dp), xy.shape[1], int(source), C.byref(sid)))
-        self._sample_sets[sid.value] = (xy.shape[1], self._sample_nval(source))
+        self._sets("sample")[sid.value] = (xy.shape[1], self._sample_nval(source))
         return sid.value
 
     def sample_create_ref(self, xgl, elem, xi_eta, source: int = 0) -> int:
@@ -416,7 +437,7 @@ class Engine:
         dp = C.POINTER(C.c_double)
         self._check(lib().hnumo_sample_create_ref(self.h, xgl.ctypes.data_as(dp), elem.ctypes.data_as(C.POINTER(C.c_int32)),
                                                   xe.ctypes.data_as(dp), elem.size, int(source), C.byref(sid)))
-        self._sample_sets[sid.value] = (elem.size, self._sample_nval(source))
+        self._sets("sample")[sid.value] = (elem.size, self._sample_nval(source))
         return sid.value
 
     def _sample_xgl(self, xgl):
@@ -425,27 +446,13 @@ class Engine:
             raise ValueError(f"xgl: {xgl.size} nodes, expected ngl = {self.dims['ngl']}")
         return xgl
 
-    @property
-    def _sample_sets(self) -> dict:
-        """id -> (M, V) of the sets created through this object (the sizes of their read-outs)."""
-        return self.__dict__.setdefault("_sample_sets_", {})
-
-    def _sample_shape(self, sid: int):
-        if sid not in self._sample_sets:
-            raise EngineError(4, f"no sample set with id {sid}")
-        return self._sample_sets[sid]
-
     def sample_plan(self, sid: int):
         """(elem (M) int32, xi_eta (2, M)) of the set."""
-        M, _ = self._sample_shape(sid)
-        elem = np.zeros(M, dtype=np.int32)
-        xe = np.zeros((2, M), order="F")
-        self._check(lib().hnumo_sample_plan(self.h, int(sid), elem.ctypes.data_as(C.POINTER(C.c_int32)), _dp(xe), M))
-        return elem, xe
+        return self._plan(lib().hnumo_sample_plan, sid, self._set_sizes("sample", sid)[0])
 
     def sample(self, sid: int):
         """(V, M): the set sampled on the device now (no sync)."""
-        M, V = self._sample_shape(sid)
+        M, V = self._set_sizes("sample", sid)
         out = np.zeros((V, M), order="F")
         self._check(lib().hnumo_sample(self.h, int(sid), _dp(out), out.size))
         return out
@@ -461,56 +468,34 @@ class Engine:
 
     def sample_series(self, sid: int, clear: bool = False):
         """(V, M, count): the recorded samples; clear empties the series afterwards."""
-        M, V = self._sample_shape(sid)
-        n = C.c_int64()
-        self._check(lib().hnumo_sample_series(self.h, int(sid), None, 0, C.byref(n), 0))
-        out = np.zeros((V, M, n.value), order="F")
-        if n.value or clear:
-            buf = out if out.size else np.zeros(1)
-            self._check(lib().hnumo_sample_series(self.h, int(sid), _dp(buf), out.size, C.byref(n), int(clear)))
-        return out
+        M, V = self._set_sizes("sample", sid)
+        return self._series(lib().hnumo_sample_series, (V, M), int(sid), clear=clear)
 
     def sample_destroy(self, sid: int):
         self._check(lib().hnumo_sample_destroy(self.h, int(sid)))
-        self._sample_sets.pop(sid, None)
+        self._sets("sample").pop(sid, None)
 
     # ---- float sets on the device state (hnumo_floats_*; mirror and helpers: hnumo/floats.py)
-    @property
-    def _float_sets(self) -> dict:
-        """id -> M of the sets created through this object."""
-        return self.__dict__.setdefault("_float_sets_", {})
-
-    def _floats_M(self, fid: int) -> int:
-        if fid not in self._float_sets:
-            raise EngineError(4, f"no float set with id {fid}")
-        return self._float_sets[fid]
-
-    @staticmethod
-    def _floats_seeds(xy, layer):
-        xy = np.asfortranarray(xy, dtype=np.float64)
-        if xy.ndim != 2 or xy.shape[0] != 2:
-            raise ValueError(f"xy: shape {xy.shape}, expected (2, M)")
+    def _floats_seeds(self, xy, layer):
+        xy = self._xy_arg(xy)
         layer = np.ascontiguousarray(np.broadcast_to(np.asarray(layer, dtype=np.int32), (xy.shape[1],)))
         return xy, layer
 
     def floats_create(self, coord, xgl, xy, layer) -> int:
         """A float set seeded at xy (2, M) in the layers `layer` (M, or one for all; 1-based), located in
         the owned elements from coord (2 or 3, npoin) and the LGL nodes xgl.  Returns its id."""
-        coord = np.asfortranarray(coord, dtype=np.float64)
-        if coord.ndim != 2 or coord.shape[1] != self.dims["npoin"]:
-            raise ValueError(f"coord: shape {coord.shape}, expected (2 or 3, {self.dims['npoin']})")
-        xgl = self._sample_xgl(xgl)
+        coord, xgl = self._coord_arg(coord), self._sample_xgl(xgl)
         xy, layer = self._floats_seeds(xy, layer)
         fid = C.c_int32(-1)
         dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         self._check(lib().hnumo_floats_create(self.h, coord.ctypes.data_as(dp), coord.shape[0], xgl.ctypes.data_as(dp),
                                               xy.ctypes.data_as(dp), layer.ctypes.data_as(ip), xy.shape[1], C.byref(fid)))
-        self._float_sets[fid.value] = xy.shape[1]
+        self._sets("float")[fid.value] = xy.shape[1]
         return fid.value
 
     def floats_get(self, fid: int) -> dict:
         """x, y, u, v (M, float64), elem, status (M, int32) in input order; u, v = the stored velocity."""
-        M = self._floats_M(fid)
+        M = self._set_sizes("float", fid)
         f = {k: np.zeros(M) for k in ("x", "y", "u", "v")}
         i = {k: np.zeros(M, dtype=np.int32) for k in ("elem", "status")}
         ip = C.POINTER(C.c_int32)
@@ -520,15 +505,11 @@ class Engine:
 
     def floats_plan(self, fid: int):
         """(elem (M) int32, xi_eta (2, M)): the floats' cached locations in input order."""
-        M = self._floats_M(fid)
-        elem = np.zeros(M, dtype=np.int32)
-        xe = np.zeros((2, M), order="F")
-        self._check(lib().hnumo_floats_plan(self.h, int(fid), elem.ctypes.data_as(C.POINTER(C.c_int32)), _dp(xe), M))
-        return elem, xe
+        return self._plan(lib().hnumo_floats_plan, fid, self._set_sizes("float", fid))
 
     def floats_set(self, fid: int, xy, layer):
         """Re-seed and relocate the set's M floats."""
-        M = self._floats_M(fid)
+        M = self._set_sizes("float", fid)
         xy, layer = self._floats_seeds(xy, layer)
         self._check(lib().hnumo_floats_set(self.h, int(fid), xy.ctypes.data_as(C.POINTER(C.c_double)),
                                            layer.ctypes.data_as(C.POINTER(C.c_int32)), xy.shape[1]))
@@ -548,18 +529,11 @@ class Engine:
 
     def floats_series(self, fid: int, clear: bool = False):
         """(5, M, count) = x, y, u, v, elem per record; clear empties the series afterwards."""
-        M = self._floats_M(fid)
-        n = C.c_int64()
-        self._check(lib().hnumo_floats_series(self.h, int(fid), None, 0, C.byref(n), 0))
-        out = np.zeros((5, M, n.value), order="F")
-        if n.value or clear:
-            buf = out if out.size else np.zeros(1)
-            self._check(lib().hnumo_floats_series(self.h, int(fid), _dp(buf), out.size, C.byref(n), int(clear)))
-        return out
+        return self._series(lib().hnumo_floats_series, (5, self._set_sizes("float", fid)), int(fid), clear=clear)
 
     def floats_destroy(self, fid: int):
         self._check(lib().hnumo_floats_destroy(self.h, int(fid)))
-        self._float_sets.pop(fid, None)
+        self._sets("float").pop(fid, None)
 
     def bench_steps(self, nsteps: int):
         t = C.c_double()

@@ -337,6 +337,44 @@ def test_two_face_ranks_in_a_local_group(case_factory):
     check_ranks([face_partition(case, 2, r, "block") for r in range(2)], case)
 
 
+def test_group_step_runs_every_observer_after_a_refused_recording(case_factory):
+    """Two ranks in a local group, each with flow statistics (every = 1, a series of one sample) and a
+    float set (every = 1).  The second group step is refused by the full statistics series (code 4: the
+    step itself succeeded), and the floats of both ranks have advanced on it all the same: they are
+    those of two steps with a series that is large enough."""
+    from hnumo.engine import Engine, EngineError, group_ti_rk_bcl, local_group
+    from hnumo.facepart import face_partition
+    case = FC.moving(case_factory, *FC.CASES[1])
+    parts = [face_partition(case, 2, r, "block") for r in range(2)]
+    xy, layer = FC.seeds(case, max_edge_elems=24)
+
+    def two_steps(capacity):
+        engines = [Engine(p) for p in parts]
+        local_group(engines)
+        sets = [FL.DeviceFloats(g, xy, layer) for g in engines]
+        for g, s in zip(engines, sets):
+            g.stats_begin(every=1, series=capacity)
+            s.begin(every=1)
+        sts = [g.state() for g in engines]
+        group_ti_rk_bcl(engines, sts)
+        if capacity >= 2:
+            group_ti_rk_bcl(engines, sts)
+        else:
+            with pytest.raises(EngineError) as ei:
+                group_ti_rk_bcl(engines, sts)
+            assert ei.value.code == 4 and "flow statistics after the step" in str(ei.value)
+        got = [s.get() for s in sets]
+        for g in engines:
+            g.close()
+        return got
+
+    want, got = two_steps(2), two_steps(1)
+    for r in range(2):
+        assert (want[r]["status"] == FL.ACTIVE).any() and want[r]["u"].any()
+        for k in ("x", "y", "u", "v", "elem", "status"):
+            assert np.array_equal(got[r][k], want[r][k]), (r, k, int((got[r][k] != want[r][k]).sum()))
+
+
 def test_two_rank_ghost_layer_partition(case_factory):
     from hnumo.partition import partition
     case = FC.moving(case_factory, *FC.CASES[1])
