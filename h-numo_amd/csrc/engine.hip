@@ -255,7 +255,19 @@ struct hnumo_engine {
     int *d_i = nullptr;                    // elem | layer | status | fresh | perm, [M] each
     int every = 0;
     Series series;
+    // migration (hnumo_floats_migrate): the tol_e in use are those of coord_scale when it is > 0; xface | arrive |
+    // iperm on the device; three boxes of M flight records (outbox 0, outbox 1, the inbox of hnumo_floats_deliver)
+    // and the two outbox counters; the outbox the next advance or arrival writes; a record the advance deferred
+    bool mig = false, settle_due = false;
+    double coord_scale = 0.0;
+    int *d_mig = nullptr;                  // xface [E][4][2] | arrive [NS] | iperm [M]
+    double *d_boxd = nullptr;              // [3][FL_FD][M]
+    int *d_boxi = nullptr;                 // [3][FL_FI][M] | count [2]
+    int parity = 0;
   } floats[FL_MAXSETS];
+  // the migrating sets' tables of a processor-face rank (float_xface; fl_xface_err: why not)
+  std::vector<int32_t> fl_xface, fl_arrive;
+  std::string fl_xface_err;
 };
 
 // the per-kernel breakdown's mark after a launch on the engine stream (no-op outside
@@ -1121,6 +1133,14 @@ static void adopt_plan(hnumo_engine *eng, const hnumo_mesh_desc *mesh, const hnu
   eng->ssprk_beta.assign(st->ssprk_beta, st->ssprk_beta + par->kstages);
   if (float_side_neighbours(mesh->face, mesh->imapl, mesh->imapr, F, ngl, E, pl.nelem_owned, eng->fl_nbr, eng->fl_nbr_err))
     eng->fl_nbr.clear();                   // (no float sets on this mesh; the step does not need them)
+  if (pl.face_halo && eng->nranks > 1 && !eng->fl_nbr.empty()) {
+    std::vector<int32_t> num, list;
+    for (const auto &nb : pl.fnb) num.push_back(nb.n);
+    for (int f : pl.sface) list.push_back(f + 1);
+    if (float_xface(mesh->face, mesh->imapl, F, ngl, pl.nelem_owned, eng->fl_nbr, (int)num.size(), num.data(), list.data(),
+                    eng->fl_xface, eng->fl_arrive, eng->fl_xface_err))
+      eng->fl_xface.clear();
+  }
 }
 
 static int open_device(hnumo_engine *eng, int *ncu) {
@@ -2259,14 +2279,38 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
   for (int i = 0; i < n; i++)
     if (rc[i]) return rc[i];
   // (the step of every engine succeeded: every engine's observers run, each on its engine's stream,
-  // whatever another one returns; the first non-zero code is returned)
+  // whatever another one returns; the first non-zero code is returned.  The migrating float sets come
+  // last: their advance needs every engine, observers_after_step leaves them out)
   int ro = 0;
   for (int i = 0; i < n; i++) {
     (void)hipSetDevice(engines[i]->device);
     const int r = observers_after_step(engines[i]);
     if (!ro) ro = r;
   }
+  for (int id = 0; id < FL_MAXSETS; id++) {
+    const auto &s = engines[0]->floats[id];
+    if (!s.used || !s.mig || s.every != 1) continue;
+    const int r = floats_group_advance(engines, n, id, engines[0]->p.dt, "float set after the step (the step itself succeeded)");
+    if (!ro) ro = r;
+  }
   return ro;
+}
+
+static bool is_group(hnumo_engine **engines, int n) {
+  if (!engines || n < 1 || !engines[0] || !engines[0]->group || (int)engines[0]->group->eng.size() != n) return false;
+  for (int i = 0; i < n; i++)
+    if (engines[i] != engines[0]->group->eng[i]) return false;
+  return true;
+}
+
+int hnumo_group_floats_migrate(hnumo_engine **engines, int n, int32_t id, int32_t on, double coord_scale) {
+  if (!is_group(engines, n)) return HNUMO_ERR_INVALID;
+  return floats_group_migrate(engines, n, id, on, coord_scale);
+}
+
+int hnumo_group_floats_advance(hnumo_engine **engines, int n, int32_t id, double dt) {
+  if (!is_group(engines, n)) return HNUMO_ERR_INVALID;
+  return floats_group_advance(engines, n, id, dt, "hnumo_group_floats_advance");
 }
 
 // Per-kernel breakdown of a step: `nsteps` direct (uncaptured) steps of the resident device state

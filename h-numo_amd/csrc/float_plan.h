@@ -33,11 +33,24 @@
 //   float's own (x, y) for the fresh evaluation).  Inactive floats are never touched again.
 // Every loop is bounded: 32 Newton iterations, 4 hops.
 //
+// Migration (processor-face ranks; include/hnumo_engine.h has the normative text).  In a migrating set
+// a location that reaches step 3 at a processor face returns FL_FLIGHT and fills a FloatFlight: the
+// float's (x, y, w) at the start of this advance, dt, the stage (0 locating p*, 1 locating p1), the
+// current target, the passes through 3 so far and the destination (k, pos) = (neighbour index, position
+// of the face in that neighbour's list).  The sender's slot becomes LEFT as before.  float_resume runs
+// the tail of the advance on the receiver from the element behind the face; MIG is a template flag, so
+// float_advance<NGL> is the text it was.
+//
 // The host part: the per-element tables (corners [E][4][2], tol_e [E], side neighbours [E][4] with
 // sides xi=-1, xi=+1, eta=-1, eta=+1: neighbour element, -1 wall, -2 off-rank), derived from face,
 // imapl, imapr by the set of local nodes on each side; validation (every failure: code 4 and a
-// message); the initial location through sample_locate; the stable sort by initial element.
+// message); the initial location through sample_locate; the stable sort by initial element; for migrating
+// sets the side table xface, the arrival table and the inverse permutation (float_xface,
+// float_inverse_perm), tol_e under a coord_scale (float_tolerances) and the host statements of the
+// two kernels (float_advance_mig_ngl, float_arrive_ngl).
 #pragma once
+#include <type_traits>
+
 #include "sample_plan.h"
 
 #if defined(__HIPCC__)
@@ -54,6 +67,9 @@ constexpr int FL_ACTIVE = 0, FL_LEFT = 1, FL_LOST = 2;
 constexpr int FL_WALL = -1, FL_OFF_RANK = -2;       // side neighbours that are no element
 constexpr int FL_MAXHOPS = 4, FL_NEWTON = 32;
 constexpr int FL_NREC = 5;                          // a record: x, y, u, v, elem
+constexpr int FL_FLIGHT = 3;                        // float_locate<true>'s answer at a processor face (never a float's status)
+constexpr int FL_MAXROUNDS = 8;                     // rounds of arrivals that settle one advance (2 locations x 4 hops)
+constexpr int FL_FD = 7, FL_FI = 6;                 // double and int32 planes of an outbox
 
 // what the three functions read: the tables of the owned elements and the state
 struct FloatField {
@@ -69,6 +85,13 @@ struct FloatField {
 struct FloatRec {
   double x, y, wx, wy, xi, eta;
   int32_t elem, layer, status, fresh;
+};
+
+// a float in flight between two ranks (planes of an outbox: x, y, wx, wy, dt, px, py | gid, layer, stage,
+// hops, k, pos)
+struct FloatFlight {
+  double x, y, wx, wy, dt, px, py;
+  int32_t gid, layer, stage, hops, k, pos;
 };
 
 HNUMO_HD inline bool float_finite(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }   // (false for a NaN)
@@ -136,9 +159,13 @@ HNUMO_HD inline void float_vel(const FloatField &f, int k, int e, double xi, dou
 }
 
 // locates (px, py) starting from element e (0-based); on return the element, its clamped (xi, eta)
-// and the target, which a wall may have moved.  Returns the status.
-HNUMO_HD inline int float_locate(const FloatField &f, double &px, double &py, int &e, double &xi, double &eta) {
-  for (int hop = 0;; hop++) {
+// and the target, which a wall may have moved.  Returns the status.  `hop`: the passes through 3 behind
+// this location (an arrival's).  MIG: a processor face listed in xface [E][4][2] gives FL_FLIGHT with
+// the target, the passes so far and (k, pos) in *fl.
+template <bool MIG = false>
+HNUMO_HD inline int float_locate(const FloatField &f, double &px, double &py, int &e, double &xi, double &eta, int hop = 0,
+                                 const int32_t *xface = nullptr, FloatFlight *fl = nullptr) {
+  for (;; hop++) {
     const double *c = f.corners + 8 * (size_t)e;
     if (!float_invert(c, px, py, xi, eta)) return FL_LOST;
     const double ax = __builtin_fabs(xi), ay = __builtin_fabs(eta);
@@ -160,6 +187,17 @@ HNUMO_HD inline int float_locate(const FloatField &f, double &px, double &py, in
       px = x[0];
       py = x[1];
     } else {
+      if constexpr (MIG) {
+        const int32_t *d = xface + 2 * (4 * (size_t)e + (in_eta ? 2 : 0) + (plus ? 1 : 0));
+        if (d[0] >= 0) {
+          fl->px = px;
+          fl->py = py;
+          fl->hops = hop + 1;
+          fl->k = d[0];
+          fl->pos = d[1];
+          return FL_FLIGHT;
+        }
+      }
       return FL_LEFT;
     }
   }
@@ -181,28 +219,50 @@ struct FloatVelPlain {
   }
 };
 
+// a location of stage `stage` ended with st != ACTIVE: the slot stops; true: the float is in flight (*fl complete
+// but for gid)
+template <bool MIG>
+HNUMO_HD inline bool float_leave(FloatRec &r, int st, double px, double py, double dt, int stage, FloatFlight *fl) {
+  if constexpr (MIG)
+    if (st == FL_FLIGHT) {
+      fl->x = r.x;
+      fl->y = r.y;
+      fl->wx = r.wx;
+      fl->wy = r.wy;
+      fl->dt = dt;
+      fl->layer = r.layer;
+      fl->stage = stage;
+      float_stop(r, FL_LEFT, px, py);
+      return true;
+    }
+  float_stop(r, st, px, py);
+  return false;
+}
+
+// float_advance's statements from a stage on, for a float that arrives (the same text, statement for statement:
+// float_advance itself stays the straight-line text its kernel has always been compiled from).  Stage 0: locate p* = (px, py) from e with `hop` passes
+// behind it, u* = vel, p1, and go on as stage 1 from there with no pass behind; stage 1: locate p1 = (px, py),
+// w = vel, the float moves.  True: in flight (MIG only).
 template <int NGL, class Vel>
-HNUMO_HD inline void float_advance(const FloatField &f, double dt, FloatRec &r, const Vel &vel) {
-  if (r.status != FL_ACTIVE) return;
+HNUMO_HD inline bool float_heun(const FloatField &f, double dt, FloatRec &r, const Vel &vel, int stage, double px, double py, int e,
+                                int hop, const int32_t *xface, FloatFlight *fl) {
   const int k = r.layer - 1;
-  int e = r.elem - 1;
-  if (r.fresh) {
-    vel.template eval<NGL>(f, k, e, r.xi, r.eta, r.wx, r.wy);
-    r.fresh = 0;
-    if (!float_finite(r.wx) || !float_finite(r.wy)) return float_stop(r, FL_LOST, r.x, r.y);
+  double xi, eta;
+  if (stage == 0) {
+    const int st = float_locate<true>(f, px, py, e, xi, eta, hop, xface, fl);
+    if (st != FL_ACTIVE) return float_leave<true>(r, st, px, py, dt, 0, fl);
+    double us, vs;
+    vel.template eval<NGL>(f, k, e, xi, eta, us, vs);
+    if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py), false;
+    px = r.x + (0.5 * dt) * (r.wx + us);
+    py = r.y + (0.5 * dt) * (r.wy + vs);
+    hop = 0;
   }
-  double px = r.x + dt * r.wx, py = r.y + dt * r.wy, xi, eta;
-  int st = float_locate(f, px, py, e, xi, eta);
-  if (st != FL_ACTIVE) return float_stop(r, st, px, py);
+  const int st = float_locate<true>(f, px, py, e, xi, eta, hop, xface, fl);
+  if (st != FL_ACTIVE) return float_leave<true>(r, st, px, py, dt, 1, fl);
   double us, vs;
   vel.template eval<NGL>(f, k, e, xi, eta, us, vs);
-  if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py);
-  px = r.x + (0.5 * dt) * (r.wx + us);
-  py = r.y + (0.5 * dt) * (r.wy + vs);
-  st = float_locate(f, px, py, e, xi, eta);
-  if (st != FL_ACTIVE) return float_stop(r, st, px, py);
-  vel.template eval<NGL>(f, k, e, xi, eta, us, vs);
-  if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py);
+  if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py), false;
   r.x = px;
   r.y = py;
   r.wx = us;
@@ -210,10 +270,76 @@ HNUMO_HD inline void float_advance(const FloatField &f, double dt, FloatRec &r, 
   r.elem = e + 1;
   r.xi = xi;
   r.eta = eta;
+  return false;
+}
+
+template <int NGL, bool MIG = false, class Vel>
+HNUMO_HD inline bool float_advance(const FloatField &f, double dt, FloatRec &r, const Vel &vel, const int32_t *xface = nullptr,
+                                   FloatFlight *fl = nullptr) {
+  if (r.status != FL_ACTIVE) return false;
+  const int k = r.layer - 1;
+  int e = r.elem - 1;
+  if (r.fresh) {
+    vel.template eval<NGL>(f, k, e, r.xi, r.eta, r.wx, r.wy);
+    r.fresh = 0;
+    if (!float_finite(r.wx) || !float_finite(r.wy)) return float_stop(r, FL_LOST, r.x, r.y), false;
+  }
+  double px = r.x + dt * r.wx, py = r.y + dt * r.wy, xi, eta;
+  int st = float_locate<MIG>(f, px, py, e, xi, eta, 0, xface, fl);
+  if (st != FL_ACTIVE) return float_leave<MIG>(r, st, px, py, dt, 0, fl);
+  double us, vs;
+  vel.template eval<NGL>(f, k, e, xi, eta, us, vs);
+  if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py), false;
+  px = r.x + (0.5 * dt) * (r.wx + us);
+  py = r.y + (0.5 * dt) * (r.wy + vs);
+  st = float_locate<MIG>(f, px, py, e, xi, eta, 0, xface, fl);
+  if (st != FL_ACTIVE) return float_leave<MIG>(r, st, px, py, dt, 1, fl);
+  vel.template eval<NGL>(f, k, e, xi, eta, us, vs);
+  if (!float_finite(us) || !float_finite(vs)) return float_stop(r, FL_LOST, px, py), false;
+  r.x = px;
+  r.y = py;
+  r.wx = us;
+  r.wy = vs;
+  r.elem = e + 1;
+  r.xi = xi;
+  r.eta = eta;
+  return false;
+}
+
+// The tail of an advance from a flight record, on the rank across the face: e (0-based) is the element behind
+// it.  r comes in as the receiver's slot (its xi, eta, elem stay if the float does not settle here) and leaves
+// as the float; true: in flight again, *fl complete but for gid.
+template <int NGL, class Vel>
+HNUMO_HD inline bool float_resume(const FloatField &f, const int32_t *xface, const FloatFlight &in, int e, FloatRec &r, const Vel &vel,
+                                  FloatFlight *fl) {
+  r.x = in.x;
+  r.y = in.y;
+  r.wx = in.wx;
+  r.wy = in.wy;
+  r.layer = in.layer;
+  r.status = FL_ACTIVE;
+  r.fresh = 0;
+  return float_heun<NGL>(f, in.dt, r, vel, in.stage, in.px, in.py, e, in.hops, xface, fl);
 }
 
 // ------------------------------------------------------------------ the host part
 inline bool float_ngl_ok(int ngl) { return ngl == 3 || ngl == 4 || ngl == 5 || ngl == 6 || ngl == 8; }
+
+// the side (0..3: xi=-1, xi=+1, eta=-1, eta=+1) all ngl nodes of face f lie on in imap(3,ngl,nface); -1 none, 4 several
+inline int float_face_side(const int32_t *imap, int ngl, int f) {
+  bool all[4] = {true, true, true, true};
+  for (int n = 0; n < ngl; n++) {
+    const int32_t i = imap[3 * ((size_t)n + (size_t)ngl * f)], j = imap[3 * ((size_t)n + (size_t)ngl * f) + 1];
+    all[0] = all[0] && i == 1;
+    all[1] = all[1] && i == ngl;
+    all[2] = all[2] && j == 1;
+    all[3] = all[3] && j == ngl;
+  }
+  int s = -1;
+  for (int t = 0; t < 4; t++)
+    if (all[t]) s = s < 0 ? t : 4;
+  return s;
+}
 
 // Side neighbours [nelem_owned][4] from face(8,nface), imapl, imapr (3,ngl,nface): the side of an
 // element that a face lies on is read from the local nodes the face lists for that element (all
@@ -227,20 +353,6 @@ inline int float_side_neighbours(const int32_t *face, const int32_t *imapl, cons
     return err = std::string(who) + ": ngl must be >= 2 and nelem_owned in 0..nelem", SP_ERR_INVALID;
   const int32_t UNSET = -3;
   nbr.assign(4 * (size_t)nelem_owned, UNSET);
-  auto side_of = [&](const int32_t *imap, int f) {
-    bool all[4] = {true, true, true, true};
-    for (int n = 0; n < ngl; n++) {
-      const int32_t i = imap[3 * ((size_t)n + (size_t)ngl * f)], j = imap[3 * ((size_t)n + (size_t)ngl * f) + 1];
-      all[0] = all[0] && i == 1;
-      all[1] = all[1] && i == ngl;
-      all[2] = all[2] && j == 1;
-      all[3] = all[3] && j == ngl;
-    }
-    int s = -1;
-    for (int t = 0; t < 4; t++)
-      if (all[t]) s = s < 0 ? t : 4;
-    return s;
-  };
   for (int f = 0; f < nface; f++) {
     const int32_t el = face[8 * (size_t)f + 6], er = face[8 * (size_t)f + 7];
     if (el < 1 || el > nelem || er > nelem)
@@ -248,7 +360,7 @@ inline int float_side_neighbours(const int32_t *face, const int32_t *imapl, cons
     for (int lr = 0; lr < 2; lr++) {
       const int32_t me = lr == 0 ? el : er, other = lr == 0 ? er : el;
       if (me < 1 || me > nelem_owned) continue;     // (a wall or processor face has no right element; ghosts hold no floats)
-      const int s = side_of(lr == 0 ? imapl : imapr, f);
+      const int s = float_face_side(lr == 0 ? imapl : imapr, ngl, f);
       if (s < 0 || s > 3)
         return err = std::string(who) + ": the nodes of face " + std::to_string(f + 1) + " are not one side of element " +
                      std::to_string(me),
@@ -291,6 +403,21 @@ struct FloatPlan {
     elem[s] = r.elem, layer[s] = r.layer, status[s] = r.status, fresh[s] = r.fresh;
   }
 };
+
+// tol_e of every element for max|coord| = maxc: (64 eps maxc) / (0.5 * shortest edge), float_geometry's own statement
+inline void float_tolerances(const std::vector<double> &corners, double maxc, std::vector<double> &tol) {
+  const double tol_x = 64.0 * std::numeric_limits<double>::epsilon() * maxc;
+  tol.resize(corners.size() / 8);
+  for (size_t e = 0; e < tol.size(); e++) {
+    const double *c = corners.data() + 8 * e;
+    double smin = INFINITY;
+    for (int m = 0; m < 4; m++) {
+      const double ex = c[2 * ((m + 1) & 3)] - c[2 * m], ey = c[2 * ((m + 1) & 3) + 1] - c[2 * m + 1];
+      smin = std::min(smin, std::sqrt(ex * ex + ey * ey));
+    }
+    tol[e] = tol_x / (0.5 * smin);
+  }
+}
 
 // corners, tol_e (sample_locate's) and the kept coord / xgl.  The bilinear-element contract and the
 // rest of the geometry's validation are sample_locate's own, run by float_seed.
@@ -405,6 +532,117 @@ inline void float_advance_all(const FloatGeom &g, const double *q, size_t npoin,
     case 5: float_advance_all_ngl<5>(f, dt, p); break;
     case 6: float_advance_all_ngl<6>(f, dt, p); break;
     default: float_advance_all_ngl<8>(f, dt, p); break;
+  }
+}
+
+// ------------------------------------------------------------------ migration, the host part
+// The side table xface [nelem_owned][4][2] and the arrival table [sum num_send_recv] of a processor-face rank,
+// from the halo lists (num_nbh neighbours, num_send_recv[k] 1-based local faces each in nbh_send_recv, in the
+// order both ranks agree on): the side of face(7) that listed face `pos` of neighbour k lies on gets (k, pos),
+// every other side (-1, -1); arrive[off_k + pos] = that element, 0-based.
+inline int float_xface(const int32_t *face, const int32_t *imapl, int nface, int ngl, int nelem_owned, const std::vector<int32_t> &nbr,
+                       int num_nbh, const int32_t *num_send_recv, const int32_t *nbh_send_recv, std::vector<int32_t> &xface,
+                       std::vector<int32_t> &arrive, std::string &err) {
+  const char *who = "hnumo_floats_migrate";
+  if (!face || !imapl) return err = std::string(who) + ": face or imapl is NULL", SP_ERR_INVALID;
+  if (num_nbh < 0 || (num_nbh > 0 && (!num_send_recv || !nbh_send_recv)))
+    return err = std::string(who) + ": num_nbh < 0, or num_send_recv or nbh_send_recv is NULL", SP_ERR_INVALID;
+  if (nelem_owned < 0 || nbr.size() != 4 * (size_t)nelem_owned)
+    return err = std::string(who) + ": the side neighbours do not cover the owned elements", SP_ERR_INVALID;
+  xface.assign(8 * (size_t)nelem_owned, -1);
+  arrive.clear();
+  size_t o = 0;
+  for (int k = 0; k < num_nbh; k++) {
+    if (num_send_recv[k] < 0) return err = std::string(who) + ": num_send_recv(" + std::to_string(k + 1) + ") < 0", SP_ERR_INVALID;
+    for (int pos = 0; pos < num_send_recv[k]; pos++, o++) {
+      const int f = nbh_send_recv[o] - 1;
+      const std::string which = "face " + std::to_string(f + 1) + " (neighbour " + std::to_string(k + 1) + ", position " +
+                                std::to_string(pos + 1) + ")";
+      if (f < 0 || f >= nface) return err = std::string(who) + ": " + which + " is out of range", SP_ERR_INVALID;
+      const int32_t el = face[8 * (size_t)f + 6];
+      if (face[8 * (size_t)f + 7] != 0 || el < 1 || el > nelem_owned)
+        return err = std::string(who) + ": " + which + " is not a processor face (face(8) = 0) of an owned element", SP_ERR_INVALID;
+      const int sd = float_face_side(imapl, ngl, f);
+      if (sd < 0 || sd > 3) return err = std::string(who) + ": the nodes of " + which + " are not one side of its element", SP_ERR_INVALID;
+      const size_t t = 4 * (size_t)(el - 1) + sd;
+      if (xface[2 * t] >= 0) return err = std::string(who) + ": " + which + " lies on a side that is listed already", SP_ERR_INVALID;
+      if (nbr[t] != FL_OFF_RANK) return err = std::string(who) + ": " + which + " lies on a side that is not off-rank", SP_ERR_INVALID;
+      xface[2 * t] = k;
+      xface[2 * t + 1] = pos;
+      arrive.push_back(el - 1);
+    }
+  }
+  return 0;
+}
+
+// iperm[input position] = the kernel's slot
+inline std::vector<int32_t> float_inverse_perm(const std::vector<int32_t> &perm) {
+  std::vector<int32_t> ip(perm.size());
+  for (size_t s = 0; s < perm.size(); s++) ip[perm[s]] = (int32_t)s;
+  return ip;
+}
+
+// what an arrival is checked for before it is run: values no sender produces would leave the hop loop unbounded
+HNUMO_HD inline bool float_flight_ok(const FloatFlight &fl, int64_t M, int nlayers, int nfaces) {
+  return fl.gid >= 0 && fl.gid < M && fl.layer >= 1 && fl.layer <= nlayers && (fl.stage == 0 || fl.stage == 1) && fl.hops >= 1 &&
+         fl.hops <= FL_MAXHOPS && fl.pos >= 0 && fl.pos < nfaces;
+}
+
+// a rank's side of a migrating set on the host: what the kernels read
+struct FloatRank {
+  const FloatGeom *g = nullptr;
+  std::vector<double> tol;               // tol_e under the set's coord_scale (g->tol without one)
+  std::vector<int32_t> xface, arrive, iperm;
+  std::vector<int> off, cnt;             // per neighbour: its segment of arrive
+  FloatField field(const double *q, size_t npoin) const {
+    FloatField f = float_field(*g, q, npoin);
+    f.tol = tol.data();
+    return f;
+  }
+};
+
+// the host statement of float_advance_kernel<NGL, 1, true>: one advance of the whole set, flights appended to out
+template <int NGL>
+inline void float_advance_mig_ngl(const FloatRank &rk, const FloatField &f, double dt, FloatPlan &p, std::vector<FloatFlight> &out) {
+  for (int64_t s = 0; s < p.M; s++) {
+    FloatRec r;
+    p.get((size_t)s, r);
+    FloatFlight fl{};
+    if (float_advance<NGL, true>(f, dt, r, FloatVelPlain{}, rk.xface.data(), &fl)) {
+      fl.gid = p.perm[s];
+      out.push_back(fl);
+    }
+    p.put((size_t)s, r);
+  }
+}
+
+// the host statement of float_arrive_kernel<NGL>: the entries of a sender's outbox addressed to neighbour index
+// want_k of the sender, which is this rank's neighbour `from`
+template <int NGL>
+inline void float_arrive_ngl(const FloatRank &rk, const FloatField &f, int nlayers, const std::vector<FloatFlight> &in, int want_k,
+                             int from, FloatPlan &p, std::vector<FloatFlight> &out) {
+  for (const FloatFlight &a : in) {
+    if (a.k != want_k || !float_flight_ok(a, p.M, nlayers, rk.cnt[from])) continue;
+    const size_t s = (size_t)rk.iperm[a.gid];
+    FloatRec r;
+    p.get(s, r);
+    FloatFlight fl{};
+    if (float_resume<NGL>(f, rk.xface.data(), a, rk.arrive[rk.off[from] + a.pos], r, FloatVelPlain{}, &fl)) {
+      fl.gid = a.gid;
+      out.push_back(fl);
+    }
+    p.put(s, r);
+  }
+}
+
+template <class F>
+inline void float_with_ngl(int ngl, F &&fn) {
+  switch (ngl) {
+    case 3: fn(std::integral_constant<int, 3>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    case 5: fn(std::integral_constant<int, 5>{}); break;
+    case 6: fn(std::integral_constant<int, 6>{}); break;
+    default: fn(std::integral_constant<int, 8>{}); break;
   }
 }
 

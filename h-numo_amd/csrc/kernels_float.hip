@@ -8,8 +8,9 @@
 //
 // Floats are SoA in the set's sorted order (by initial element): x, y, wx, wy, xi, eta doubles and
 // elem, layer, status, fresh int32, so a wave moves contiguous lines and its lanes start in the same
-// few elements.  No atomics, nothing between workgroups, no LDS; every loop over registers has
-// compile-time bounds, the Newton and hop loops are bounded by 32 and 4.
+// few elements.  No atomics (but the migrating sets' one integer add per wave, below), nothing between
+// workgroups, no LDS; every loop over registers has compile-time bounds, the Newton and hop loops are
+// bounded by 32 and 4.
 //
 // float_advance_kernel<NGL, G>: G lanes per float.  G = 1 is the mapping in use; G > 1 was measured
 // beside it (HNUMO_FLOAT_ROWS=1 with HNUMO_EXPERIMENTS=1) and is slower wherever the
@@ -22,6 +23,15 @@
 //          is still one lane's, so the bits are those of G = 1.  Lane 0 of the group stores.
 // float_record_kernel appends a record (x, y, u, v, elem) to the planar series at the floats' input
 // positions.
+//
+// Migrating sets (processor-face ranks): float_advance_kernel<NGL, 1, true> is the same advance with
+// float_plan.h's MIG flag: a lane whose float reaches a processor face appends its flight record to the
+// rank's outbox -- SoA, 7 double and 6 int32 planes of capacity M -- by one integer atomicAdd per wave
+// (ballot, lanes ranked by the ballot prefix).  The order of an outbox is not deterministic and nothing
+// depends on it: float_arrive_kernel<NGL>, one lane per entry of a sender's outbox, drops the entries
+// addressed to another rank, resumes the float in the element behind the face (float_resume) and stores
+// it in its own slot iperm[gid]; a float that goes into flight again is appended to the receiver's outbox
+// of the next round.  No LDS, no floating-point atomics.  <NGL, G, false> is the kernel as it was.
 #include "engine_internal.h"
 #include "float_plan.h"
 
@@ -35,6 +45,35 @@ struct FloatArgs {
   double *rec;                             // [FL_NREC][M] (float_record_kernel)
   double dt;
   size_t M;
+};
+
+// an outbox: planes [FL_FD][cap] (x, y, wx, wy, dt, px, py) and [FL_FI][cap] (gid, layer, stage, hops, k, pos)
+struct FloatBox {
+  double *d;
+  int *i;
+  int *count;
+  size_t cap;
+};
+
+struct FloatMigArgs {
+  FloatArgs a;
+  const int *xface;                        // [E][4][2]
+  FloatBox out;
+};
+
+struct FloatArriveArgs {
+  FloatArgs a;                             // the receiver's floats and field
+  const int *xface, *arrive, *iperm;       // the receiver's tables; arrive at the sender's segment
+  FloatBox in, out;                        // the sender's outbox of this round, the receiver's of the next
+  int n;                                   // entries of `in` (the host has read the count)
+  int want_k;                              // the k that addresses the receiver in `in`
+  int nfaces, nlayers;                     // faces the two ranks share; layers
+};
+
+struct FloatMarkArgs {
+  FloatArgs a;
+  const int *gid, *iperm;
+  int n, status;                           // status LEFT: release ACTIVE floats; LOST: whatever they are
 };
 
 constexpr int fl_group(int ngl) { return ngl <= 4 ? 4 : 8; }
@@ -79,19 +118,25 @@ struct FloatVelRows {
   }
 };
 
-template <int NGL, int G>
-__global__ void __launch_bounds__(FL_BLOCK) float_advance_kernel(FloatArgs a) {
-  static_assert(G == 1 || (G >= NGL && FL_BLOCK % G == 0 && 64 % G == 0), "a float's lanes lie in one wave");
-  const size_t s = ((size_t)blockIdx.x * FL_BLOCK + threadIdx.x) / G;
-  if (s >= a.M) return;
-  if (a.status[s] != FL_ACTIVE) return;
-  FloatRec r{a.x[s], a.y[s], a.wx[s], a.wy[s], a.xi[s], a.eta[s], a.elem[s], a.layer[s], FL_ACTIVE, a.fresh[s]};
-  if constexpr (G == 1) {
-    float_advance<NGL>(a.f, a.dt, r, FloatVelPlain{});
-  } else {
-    float_advance<NGL>(a.f, a.dt, r, FloatVelRows<G>{(int)(threadIdx.x % G)});
-    if (threadIdx.x % G) return;
-  }
+// appends the flight records of the lanes with `go`: one atomicAdd per wave, lanes ranked by the ballot prefix
+__device__ inline void float_box_append(const FloatBox &b, bool go, const FloatFlight &fl) {
+  const unsigned long long m = __ballot(go);
+  if (!go) return;
+  const int lane = (int)__lane_id(), leader = __ffsll((long long)m) - 1;
+  int base = 0;
+  if (lane == leader) base = atomicAdd(b.count, __popcll(m));
+  base = __shfl(base, leader);
+  const size_t t = (size_t)base + (size_t)__popcll(m & ((1ull << lane) - 1ull));
+  if (t >= b.cap) return;                  // (a float is in flight once: an outbox never holds more than M)
+  const double d[FL_FD] = {fl.x, fl.y, fl.wx, fl.wy, fl.dt, fl.px, fl.py};
+  const int i[FL_FI] = {fl.gid, fl.layer, fl.stage, fl.hops, fl.k, fl.pos};
+#pragma unroll
+  for (int v = 0; v < FL_FD; v++) b.d[v * b.cap + t] = d[v];
+#pragma unroll
+  for (int v = 0; v < FL_FI; v++) b.i[v * b.cap + t] = i[v];
+}
+
+__device__ inline void float_store(const FloatArgs &a, size_t s, const FloatRec &r) {
   a.x[s] = r.x;
   a.y[s] = r.y;
   a.wx[s] = r.wx;
@@ -101,6 +146,74 @@ __global__ void __launch_bounds__(FL_BLOCK) float_advance_kernel(FloatArgs a) {
   a.elem[s] = r.elem;
   a.status[s] = r.status;
   a.fresh[s] = r.fresh;
+}
+
+template <int NGL, int G, bool MIG>
+__global__ void __launch_bounds__(FL_BLOCK) float_advance_kernel(std::conditional_t<MIG, FloatMigArgs, FloatArgs> arg) {
+  if constexpr (MIG) {
+    static_assert(G == 1, "migrating sets use the one-lane mapping");
+    const FloatArgs &a = arg.a;
+    const size_t s = (size_t)blockIdx.x * FL_BLOCK + threadIdx.x;
+    bool go = false;
+    FloatFlight fl{};
+    if (s < a.M && a.status[s] == FL_ACTIVE) {
+      FloatRec r{a.x[s], a.y[s], a.wx[s], a.wy[s], a.xi[s], a.eta[s], a.elem[s], a.layer[s], FL_ACTIVE, a.fresh[s]};
+      go = float_advance<NGL, true>(a.f, a.dt, r, FloatVelPlain{}, arg.xface, &fl);
+      fl.gid = a.perm[s];
+      float_store(a, s, r);
+    }
+    float_box_append(arg.out, go, fl);
+  } else {
+    static_assert(G == 1 || (G >= NGL && FL_BLOCK % G == 0 && 64 % G == 0), "a float's lanes lie in one wave");
+    const FloatArgs &a = arg;
+    const size_t s = ((size_t)blockIdx.x * FL_BLOCK + threadIdx.x) / G;
+    if (s >= a.M) return;
+    if (a.status[s] != FL_ACTIVE) return;
+    FloatRec r{a.x[s], a.y[s], a.wx[s], a.wy[s], a.xi[s], a.eta[s], a.elem[s], a.layer[s], FL_ACTIVE, a.fresh[s]};
+    if constexpr (G == 1) {
+      float_advance<NGL>(a.f, a.dt, r, FloatVelPlain{});
+    } else {
+      float_advance<NGL>(a.f, a.dt, r, FloatVelRows<G>{(int)(threadIdx.x % G)});
+      if (threadIdx.x % G) return;
+    }
+    float_store(a, s, r);
+  }
+}
+
+template <int NGL>
+__global__ void __launch_bounds__(FL_BLOCK) float_arrive_kernel(FloatArriveArgs g) {
+  const FloatArgs &a = g.a;
+  const size_t t = (size_t)blockIdx.x * FL_BLOCK + threadIdx.x;
+  bool go = false;
+  FloatFlight fl{};
+  if (t < (size_t)g.n && g.in.i[4 * g.in.cap + t] == g.want_k) {
+    const double *d = g.in.d + t;
+    const int *i = g.in.i + t;
+    const size_t c = g.in.cap;
+    const FloatFlight in{d[0], d[c], d[2 * c], d[3 * c], d[4 * c], d[5 * c], d[6 * c], i[0], i[c], i[2 * c], i[3 * c], i[4 * c], i[5 * c]};
+    if (float_flight_ok(in, (int64_t)a.M, g.nlayers, g.nfaces)) {
+      const size_t s = (size_t)g.iperm[in.gid];
+      FloatRec r{a.x[s], a.y[s], a.wx[s], a.wy[s], a.xi[s], a.eta[s], a.elem[s], in.layer, FL_ACTIVE, 0};
+      go = float_resume<NGL>(a.f, g.xface, in, g.arrive[in.pos], r, FloatVelPlain{}, &fl);
+      fl.gid = in.gid;
+      float_store(a, s, r);
+    }
+  }
+  float_box_append(g.out, go, fl);
+}
+
+// the floats gid[0..n) of the input become `status` with elem 0, w 0 where they are: LEFT releases the ACTIVE ones
+// (a seed that another rank keeps), LOST is for a float still in flight after the last round
+__global__ void __launch_bounds__(FL_BLOCK) float_mark_kernel(FloatMarkArgs g) {
+  const size_t t = (size_t)blockIdx.x * FL_BLOCK + threadIdx.x;
+  if (t >= (size_t)g.n) return;
+  const int m = g.gid[t];
+  if (m < 0 || (size_t)m >= g.a.M) return;
+  const size_t s = (size_t)g.iperm[m];
+  if (g.status == FL_LEFT && g.a.status[s] != FL_ACTIVE) return;
+  g.a.status[s] = g.status;
+  g.a.elem[s] = 0;
+  g.a.wx[s] = g.a.wy[s] = 0.0;
 }
 
 __global__ void __launch_bounds__(FL_BLOCK) float_record_kernel(FloatArgs a) {

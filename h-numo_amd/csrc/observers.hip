@@ -657,7 +657,8 @@ using FloatSet = hnumo_engine::FloatSet;
 
 static void floats_free(hnumo_engine *eng, int id) {
   auto &s = eng->floats[id];
-  dfree(s.d_geo, s.d_nbr, s.d_f, s.d_i);
+  dfree(s.d_geo, s.d_nbr, s.d_f, s.d_i, s.d_mig, s.d_boxi);
+  dfree(s.d_boxd);
   series_free(s.series);
   s = FloatSet{};
 }
@@ -719,6 +720,13 @@ extern "C" int hnumo_floats_create(hnumo_engine *eng, const double *coord, int32
   return HNUMO_OK;
 }
 
+// the inverse permutation of a migrating set, behind xface and arrive in d_mig
+static bool floats_upload_iperm(hnumo_engine *eng, FloatSet &s) {
+  const std::vector<int32_t> ip = float_inverse_perm(s.perm);
+  return hipMemcpy(s.d_mig + eng->fl_xface.size() + eng->fl_arrive.size(), ip.data(), ip.size() * sizeof(int), hipMemcpyHostToDevice) ==
+         hipSuccess;
+}
+
 extern "C" int hnumo_floats_set(hnumo_engine *eng, int32_t id, const double *xy, const int32_t *layer, int64_t M) {
   if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_set");
@@ -734,6 +742,7 @@ extern "C" int hnumo_floats_set(hnumo_engine *eng, int32_t id, const double *xy,
     return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_set: upload failed");
   }
   s->perm = std::move(pl.perm);
+  if (s->mig && !floats_upload_iperm(eng, *s)) return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_set: upload failed");
   return HNUMO_OK;
 }
 
@@ -763,6 +772,13 @@ static int floats_record(hnumo_engine *eng, FloatSet &s, int id, const char *who
   return HNUMO_OK;
 }
 
+// box 0, 1: the outboxes (their counters behind the int planes); 2: the inbox of hnumo_floats_deliver
+static FloatBox floats_box(const FloatSet &s, int which) {
+  const size_t M = (size_t)s.M;
+  return FloatBox{s.d_boxd + (size_t)which * FL_FD * M, s.d_boxi + (size_t)which * FL_FI * M,
+                  which < 2 ? s.d_boxi + 3 * FL_FI * M + which : nullptr, M};
+}
+
 // one advance of the set on the state on the device now, and the record that is due after it
 static int floats_advance(hnumo_engine *eng, FloatSet &s, int id, double dt, const char *who) {
   if (!eng->has_state)
@@ -770,13 +786,27 @@ static int floats_advance(hnumo_engine *eng, FloatSet &s, int id, double dt, con
   if (!float_finite(dt)) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": dt is not finite");
   FloatArgs a = floats_args(eng, s);
   a.dt = dt;
+  if (s.mig) {
+    // flights go to the outbox of the current parity; the record that falls due waits for the arrivals
+    // (floats_group_advance, or hnumo_floats_settle on a host that carries the records itself)
+    FloatMigArgs m{a, s.d_mig, floats_box(s, s.parity)};
+    HIPCHK(hipMemsetAsync(m.out.count, 0, sizeof(int), eng->stream));
+    with_ngl(eng->ngl, [&](auto ngl) {
+      constexpr int NGL = decltype(ngl)::value;
+      hipLaunchKernelGGL((float_advance_kernel<NGL, 1, true>), dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+                         eng->stream, m);
+    });
+    HIPCHK(hipGetLastError());
+    if (series_due(s.series)) s.settle_due = true;
+    return HNUMO_OK;
+  }
   with_ngl(eng->ngl, [&](auto ngl) {
     constexpr int NGL = decltype(ngl)::value, G = fl_group(NGL);
     if (eng->fl_rows)
-      hipLaunchKernelGGL((float_advance_kernel<NGL, G>), dim3((unsigned)((a.M * G + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+      hipLaunchKernelGGL((float_advance_kernel<NGL, G, false>), dim3((unsigned)((a.M * G + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
                          eng->stream, a);
     else
-      hipLaunchKernelGGL((float_advance_kernel<NGL, 1>), dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+      hipLaunchKernelGGL((float_advance_kernel<NGL, 1, false>), dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
                          eng->stream, a);
   });
   HIPCHK(hipGetLastError());
@@ -804,6 +834,7 @@ extern "C" int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, 
   HIPCHK(hipSetDevice(eng->device));
   HIPCHK(hipStreamSynchronize(eng->stream));  // (a record in flight writes the old series)
   s->every = 0;
+  s->settle_due = false;
   // (record_every holds with capacity 0 too: the record that falls due is then refused as into a full series)
   if (series_begin(eng, s->series, FL_NREC * (size_t)s->M, record_every, capacity, false) != hipSuccess)
     return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_begin: device allocation failed");
@@ -879,6 +910,297 @@ extern "C" int hnumo_floats_destroy(hnumo_engine *eng, int32_t id) {
   return HNUMO_OK;
 }
 
+// ------------------------------------------------------------------ float sets: migration between ranks
+// the index of `rank` among eng's processor-face neighbours, or -1
+static int floats_nb_index(const hnumo_engine *eng, int rank) {
+  for (size_t k = 0; k < eng->fnb.size(); k++)
+    if (eng->fnb[k].rank == rank) return (int)k;
+  return -1;
+}
+
+// the tol_e the set locates with from now on: the rank's own, or those of coord_scale
+static int floats_upload_tol(hnumo_engine *eng, FloatSet &s, double scale) {
+  std::vector<double> tol = s.geom.tol;
+  if (scale > 0.0) float_tolerances(s.geom.corners, scale, tol);
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight reads the old ones)
+  if (!tol.empty()) HIPCHK(hipMemcpy(s.d_geo + 8 * tol.size(), tol.data(), tol.size() * sizeof(double), hipMemcpyHostToDevice));
+  s.coord_scale = scale;
+  return HNUMO_OK;
+}
+
+static int floats_migrate(hnumo_engine *eng, int32_t id, int32_t on, double scale, const char *who) {
+  auto *s = floats_set(eng, id, who);
+  if (!s) return HNUMO_ERR_INVALID;
+  if (!eng->face_halo || eng->nranks < 2)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": floats migrate across processor faces: the engine needs a processor-face "
+                                            "halo with nranks > 1 (not a single rank, a ghost-layer partition or the self-neighbour emulation)");
+  if (!(scale >= 0.0) || !float_finite(scale))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": coord_scale must be finite and >= 0");
+  if (!eng->fl_xface_err.empty()) return fail(eng, HNUMO_ERR_INVALID, eng->fl_xface_err);
+  HIPCHK(hipSetDevice(eng->device));
+  if (on && !s->d_mig) {
+    const size_t M = (size_t)s->M, nx = eng->fl_xface.size(), na = eng->fl_arrive.size();
+    bool ok = hipMalloc((void **)&s->d_mig, (nx + na + M) * sizeof(int)) == hipSuccess &&
+              hipMalloc((void **)&s->d_boxd, 3 * FL_FD * M * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&s->d_boxi, (3 * FL_FI * M + 2) * sizeof(int)) == hipSuccess;
+    ok = ok && (nx == 0 || hipMemcpy(s->d_mig, eng->fl_xface.data(), nx * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
+         (na == 0 || hipMemcpy(s->d_mig + nx, eng->fl_arrive.data(), na * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
+         floats_upload_iperm(eng, *s) && hipMemset(s->d_boxi + 3 * FL_FI * M, 0, 2 * sizeof(int)) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      dfree(s->d_mig, s->d_boxi);
+      dfree(s->d_boxd);
+      return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
+    }
+  }
+  if (int rc = floats_upload_tol(eng, *s, on ? scale : 0.0)) return rc;
+  s->mig = on != 0;
+  s->settle_due = false;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_migrate(hnumo_engine *eng, int32_t id, int32_t on, double coord_scale) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  return floats_migrate(eng, id, on, coord_scale, "hnumo_floats_migrate");
+}
+
+// floats idx[0..n) (input positions) become `status` where they are, elem 0, w 0 (float_mark_kernel); d_idx: on the device
+static int floats_mark(hnumo_engine *eng, FloatSet &s, const int *d_idx, int n, int status) {
+  if (n <= 0) return HNUMO_OK;
+  FloatMarkArgs g{floats_args(eng, s), d_idx, s.d_mig + eng->fl_xface.size() + eng->fl_arrive.size(), n, status};
+  hipLaunchKernelGGL(float_mark_kernel, dim3((unsigned)((n + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0, eng->stream, g);
+  HIPCHK(hipGetLastError());
+  return HNUMO_OK;
+}
+
+static int floats_release(hnumo_engine *eng, FloatSet &s, const int32_t *idx, int64_t n, const char *who) {
+  if (n < 0 || (n > 0 && !idx)) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": idx is NULL or n < 0");
+  if (!s.mig) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set does not migrate (hnumo_floats_migrate)");
+  for (int64_t t = 0; t < n; t++)
+    if (idx[t] < 0 || idx[t] >= s.M)
+      return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": idx(" + std::to_string(t + 1) + ") is outside 0..M-1");
+  if (n == 0) return HNUMO_OK;
+  // (the inbox's gid plane carries the list; nothing else uses the inbox between two calls)
+  FloatBox in = floats_box(s, 2);
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipMemcpy(in.i, idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  if (int rc = floats_mark(eng, s, in.i, (int)n, FL_LEFT)) return rc;
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_release(hnumo_engine *eng, int32_t id, const int32_t *idx, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_release");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return floats_release(eng, *s, idx, n, "hnumo_floats_release");
+}
+
+// the arrivals on eng of the n entries of `in` whose k is want_k; they come across the faces eng shares with its
+// neighbour `from`; flights that go on are appended to eng's outbox of the other parity
+static int floats_arrive(hnumo_engine *eng, FloatSet &s, const FloatBox &in, int n, int want_k, int from) {
+  if (n <= 0) return HNUMO_OK;
+  FloatArriveArgs g{};
+  g.a = floats_args(eng, s);
+  g.xface = s.d_mig;
+  g.arrive = s.d_mig + eng->fl_xface.size() + eng->fnb[from].off;
+  g.iperm = s.d_mig + eng->fl_xface.size() + eng->fl_arrive.size();
+  g.in = in;
+  g.out = floats_box(s, s.parity ^ 1);
+  g.n = n;
+  g.want_k = want_k;
+  g.nfaces = eng->fnb[from].n;
+  g.nlayers = eng->L;
+  with_ngl(eng->ngl, [&](auto ngl) {
+    hipLaunchKernelGGL((float_arrive_kernel<decltype(ngl)::value>), dim3((unsigned)((n + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0,
+                       eng->stream, g);
+  });
+  HIPCHK(hipGetLastError());
+  return HNUMO_OK;
+}
+
+// the record an advance of a migrating set deferred
+static int floats_settle(hnumo_engine *eng, FloatSet &s, int id, const char *who) {
+  if (!s.settle_due) return HNUMO_OK;
+  s.settle_due = false;
+  return floats_record(eng, s, id, who);
+}
+
+// every engine holds the set `id` with the same M (and it migrates), or the refusal, on the engine at fault
+static int floats_group_sets(hnumo_engine **engines, int n, int32_t id, const char *who, bool need_mig) {
+  for (int i = 0; i < n; i++) {
+    auto *s = floats_set(engines[i], id, who);
+    if (!s) return HNUMO_ERR_INVALID;
+    if (s->M != engines[0]->floats[id].M)
+      return fail(engines[i], HNUMO_ERR_INVALID, std::string(who) + ": float set " + std::to_string(id) + " has another M on rank " +
+                                                     std::to_string(i) + " than on rank 0 (every rank creates it from the same xy)");
+    if (need_mig && !s->mig)
+      return fail(engines[i], HNUMO_ERR_INVALID, std::string(who) + ": float set " + std::to_string(id) + " does not migrate on rank " +
+                                                     std::to_string(i) + " (hnumo_group_floats_migrate)");
+  }
+  return HNUMO_OK;
+}
+
+// hnumo_group_floats_migrate: the same on every engine; on: a seed ACTIVE on several ranks stays on the lowest
+static int floats_group_migrate(hnumo_engine **engines, int n, int32_t id, int32_t on, double scale) {
+  const char *who = "hnumo_group_floats_migrate";
+  if (int rc = floats_group_sets(engines, n, id, who, false)) return rc;
+  for (int i = 0; i < n; i++)
+    if (int rc = floats_migrate(engines[i], id, on, scale, who)) return rc;
+  if (!on) return HNUMO_OK;
+  const size_t M = (size_t)engines[0]->floats[id].M;
+  std::vector<char> held(M, 0);
+  std::vector<int32_t> st(M), idx;
+  for (int i = 0; i < n; i++) {
+    if (int rc = hnumo_floats_get(engines[i], id, nullptr, nullptr, nullptr, nullptr, nullptr, st.data(), (int64_t)M)) return rc;
+    idx.clear();
+    for (size_t m = 0; m < M; m++)
+      if (st[m] == FL_ACTIVE) {
+        if (held[m]) idx.push_back((int32_t)m);
+        held[m] = 1;
+      }
+    if (int rc = floats_release(engines[i], engines[i]->floats[id], idx.data(), (int64_t)idx.size(), who)) return rc;
+  }
+  return HNUMO_OK;
+}
+
+// hnumo_group_floats_advance, and the migrating sets' part of a group step: every engine's advance, then rounds of
+// arrivals until no float is in flight, then the records that fell due.  The synchronisation that starts a round is
+// the ordering between the engines' streams: an outbox is read only after its writer has drained, and written again
+// only two rounds later.
+static int floats_group_advance(hnumo_engine **engines, int n, int32_t id, double dt, const char *who) {
+  if (int rc = floats_group_sets(engines, n, id, who, true)) return rc;
+  for (int i = 0; i < n; i++) {
+    hnumo_engine *eng = engines[i];
+    HIPCHK(hipSetDevice(eng->device));
+    if (int rc = floats_advance(eng, eng->floats[id], id, dt, who)) return rc;
+  }
+  std::vector<int> cnt(n);
+  for (int round = 0;; round++) {
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+      hnumo_engine *eng = engines[i];
+      HIPCHK(hipSetDevice(eng->device));
+      HIPCHK(hipStreamSynchronize(eng->stream));
+      auto &s = eng->floats[id];
+      HIPCHK(hipMemcpy(&cnt[i], floats_box(s, s.parity).count, sizeof(int), hipMemcpyDeviceToHost));
+      cnt[i] = std::min<int64_t>(std::max(cnt[i], 0), s.M);
+      any = any || cnt[i] > 0;
+    }
+    if (!any) break;
+    if (round == FL_MAXROUNDS) {
+      // (cannot happen: every flight uses up a hop and an advance has 2 x 4) what is still in flight is LOST, where it left
+      for (int i = 0; i < n; i++) {
+        auto &s = engines[i]->floats[id];
+        if (int rc = floats_mark(engines[i], s, floats_box(s, s.parity).i, cnt[i], FL_LOST)) return rc;
+      }
+      break;
+    }
+    for (int i = 0; i < n; i++) {
+      hnumo_engine *eng = engines[i];
+      auto &s = eng->floats[id];
+      HIPCHK(hipSetDevice(eng->device));
+      HIPCHK(hipMemsetAsync(floats_box(s, s.parity ^ 1).count, 0, sizeof(int), eng->stream));
+      for (size_t k = 0; k < eng->fnb.size(); k++) {
+        hnumo_engine *from = engines[eng->fnb[k].rank];
+        const int me = floats_nb_index(from, eng->rank);
+        if (cnt[from->rank] == 0 || me < 0) continue;
+        auto &fs = from->floats[id];
+        if (int rc = floats_arrive(eng, s, floats_box(fs, fs.parity), cnt[from->rank], me, (int)k)) return rc;
+      }
+    }
+    for (int i = 0; i < n; i++) engines[i]->floats[id].parity ^= 1;
+  }
+  int rc = 0;
+  for (int i = 0; i < n; i++) {
+    hnumo_engine *eng = engines[i];
+    HIPCHK(hipSetDevice(eng->device));
+    const int r = floats_settle(eng, eng->floats[id], id, who);
+    if (!rc) rc = r;
+  }
+  return rc;
+}
+
+// ---- for a host that carries the flight records itself (one engine per process)
+extern "C" int hnumo_floats_outbox(hnumo_engine *eng, int32_t id, double *d, int32_t *i, int64_t cap, int64_t *count) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_floats_outbox";
+  auto *s = floats_set(eng, id, who);
+  if (!s) return HNUMO_ERR_INVALID;
+  if (!s->mig) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set does not migrate (hnumo_floats_migrate)");
+  if (!count) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": count is NULL");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  const FloatBox b = floats_box(*s, s->parity);
+  int n = 0;
+  HIPCHK(hipMemcpy(&n, b.count, sizeof(int), hipMemcpyDeviceToHost));
+  n = (int)std::min<int64_t>(std::max(n, 0), s->M);
+  if (cap < n || (n > 0 && (!d || !i)))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": d(cap,7), i(cap,6) hold cap = " + std::to_string(cap) +
+                                            " records, the outbox has " + std::to_string(n) + " (nothing taken)");
+  const size_t M = (size_t)s->M;
+  std::vector<double> hd(FL_FD * M);
+  std::vector<int32_t> hi(FL_FI * M);
+  if (n > 0) {
+    for (int v = 0; v < FL_FD; v++) HIPCHK(hipMemcpy(hd.data() + v * M, b.d + v * M, n * sizeof(double), hipMemcpyDeviceToHost));
+    for (int v = 0; v < FL_FI; v++) HIPCHK(hipMemcpy(hi.data() + v * M, b.i + v * M, n * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  // sorted by gid (the order on the device is not deterministic); k leaves as the destination rank
+  std::vector<int> ord(n);
+  for (int t = 0; t < n; t++) ord[t] = t;
+  std::sort(ord.begin(), ord.end(), [&](int a, int c) { return hi[a] < hi[c]; });
+  for (int t = 0; t < n; t++) {
+    for (int v = 0; v < FL_FD; v++) d[(size_t)v * cap + t] = hd[v * M + ord[t]];
+    for (int v = 0; v < FL_FI; v++) i[(size_t)v * cap + t] = hi[v * M + ord[t]];
+    const int k = hi[4 * M + ord[t]];
+    i[(size_t)4 * cap + t] = k >= 0 && k < (int)eng->fnb.size() ? eng->fnb[k].rank : -1;
+  }
+  *count = n;
+  s->parity ^= 1;
+  HIPCHK(hipMemsetAsync(floats_box(*s, s->parity).count, 0, sizeof(int), eng->stream));
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_deliver(hnumo_engine *eng, int32_t id, int32_t src_rank, const double *d, const int32_t *i, int64_t cap,
+                                    int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_floats_deliver";
+  auto *s = floats_set(eng, id, who);
+  if (!s) return HNUMO_ERR_INVALID;
+  if (!s->mig) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set does not migrate (hnumo_floats_migrate)");
+  const int from = floats_nb_index(eng, src_rank);
+  if (from < 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": rank " + std::to_string(src_rank) + " shares no processor face with this rank");
+  if (n < 0 || n > s->M || cap < n || (n > 0 && (!d || !i)))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": n must be in 0..M and <= cap, d(cap,7) and i(cap,6) given");
+  for (int64_t t = 0; t < n; t++) {
+    const FloatFlight fl{0, 0, 0, 0, 0, 0, 0, i[t], i[cap + t], i[2 * cap + t], i[3 * cap + t], i[4 * cap + t], i[5 * cap + t]};
+    if (fl.k == eng->rank && !float_flight_ok(fl, s->M, eng->L, eng->fnb[from].n))
+      return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": record " + std::to_string(t + 1) + " is no flight record (gid, layer, stage, hops or pos out of range)");
+  }
+  if (n == 0) return HNUMO_OK;
+  if (!eng->has_state) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (the arrivals of the last delivery read the inbox)
+  const FloatBox in = floats_box(*s, 2);
+  const size_t M = (size_t)s->M;
+  for (int v = 0; v < FL_FD; v++) HIPCHK(hipMemcpy(in.d + v * M, d + (size_t)v * cap, n * sizeof(double), hipMemcpyHostToDevice));
+  for (int v = 0; v < FL_FI; v++) HIPCHK(hipMemcpy(in.i + v * M, i + (size_t)v * cap, n * sizeof(int), hipMemcpyHostToDevice));
+  // (the flights of these arrivals join the outbox of the current parity, which hnumo_floats_outbox has just emptied)
+  s->parity ^= 1;
+  const int rc = floats_arrive(eng, *s, in, (int)n, eng->rank, from);
+  s->parity ^= 1;
+  return rc;
+}
+
+extern "C" int hnumo_floats_settle(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_settle");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return floats_settle(eng, *s, id, "hnumo_floats_settle");
+}
+
 // ------------------------------------------------------------------ after a successful step
 // Called once run_steps has returned 0 (so a step redone on per-stage launches is observed once), in
 // this order: the statistics' sample; the vorticity series' sample; the sample sets' recordings, which
@@ -900,7 +1222,9 @@ static int observers_after_step(hnumo_engine *eng) {
   }
   for (int id = 0; id < FL_MAXSETS; id++) {
     auto &s = eng->floats[id];
-    if (s.used && s.every == 1) run(floats_advance(eng, s, id, eng->p.dt, "float set after the step (the step itself succeeded)"));
+    // (a migrating set of a grouped engine is advanced by the group, after every engine's observers)
+    if (s.used && s.every == 1 && !(s.mig && eng->comm_mode == 1))
+      run(floats_advance(eng, s, id, eng->p.dt, "float set after the step (the step itself succeeded)"));
   }
   return rc;
 }

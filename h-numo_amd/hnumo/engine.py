@@ -99,6 +99,13 @@ def lib():
         L.hnumo_floats_record.argtypes = [vp, i32]
         L.hnumo_floats_series.argtypes = [vp, i32, dp, i64, C.POINTER(i64), i32]
         L.hnumo_floats_destroy.argtypes = [vp, i32]
+        L.hnumo_floats_migrate.argtypes = [vp, i32, i32, C.c_double]
+        L.hnumo_floats_release.argtypes = [vp, i32, ip, i64]
+        L.hnumo_floats_outbox.argtypes = [vp, i32, dp, ip, i64, C.POINTER(i64)]
+        L.hnumo_floats_deliver.argtypes = [vp, i32, i32, dp, ip, i64, i64]
+        L.hnumo_floats_settle.argtypes = [vp, i32]
+        L.hnumo_group_floats_migrate.argtypes = [C.POINTER(vp), C.c_int, i32, i32, C.c_double]
+        L.hnumo_group_floats_advance.argtypes = [C.POINTER(vp), C.c_int, i32, C.c_double]
         _lib = L
     return _lib
 
@@ -535,6 +542,38 @@ class Engine:
         self._check(lib().hnumo_floats_destroy(self.h, int(fid)))
         self._sets("float").pop(fid, None)
 
+    def floats_migrate(self, fid: int, on: bool = True, coord_scale: float = 0.0):
+        """The set hands floats that reach a processor face to the rank across it (processor-face ranks)."""
+        self._check(lib().hnumo_floats_migrate(self.h, int(fid), int(bool(on)), float(coord_scale)))
+
+    def floats_release(self, fid: int, idx):
+        """The floats at the 0-based input positions idx that are ACTIVE on this rank become LEFT."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        self._check(lib().hnumo_floats_release(self.h, int(fid), idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size))
+
+    def floats_outbox(self, fid: int):
+        """(d (7, n), i (6, n)): the flight records waiting on this rank, sorted by gid; d = x, y, wx, wy, dt,
+        px, py and i = gid, layer, stage, hops, destination rank, pos.  The outbox is empty afterwards."""
+        M = self._set_sizes("float", fid)
+        d, i = np.zeros((7, M)), np.zeros((6, M), dtype=np.int32)
+        n = C.c_int64()
+        self._check(lib().hnumo_floats_outbox(self.h, int(fid), d.ctypes.data_as(C.POINTER(C.c_double)),
+                                              i.ctypes.data_as(C.POINTER(C.c_int32)), M, C.byref(n)))
+        return d[:, :n.value].copy(), i[:, :n.value].copy()
+
+    def floats_deliver(self, fid: int, src_rank: int, d, i):
+        """Runs the arrivals of the flight records (d (7, n), i (6, n)) that rank src_rank sent."""
+        d, i = np.ascontiguousarray(d, dtype=np.float64), np.ascontiguousarray(i, dtype=np.int32)
+        n = d.shape[1]
+        if d.ndim != 2 or d.shape[0] != 7 or i.shape != (6, d.shape[1]):
+            raise ValueError(f"deliver: d {d.shape}, i {i.shape}, expected (7, n) and (6, n)")
+        self._check(lib().hnumo_floats_deliver(self.h, int(fid), int(src_rank), d.ctypes.data_as(C.POINTER(C.c_double)),
+                                               i.ctypes.data_as(C.POINTER(C.c_int32)), n, n))
+
+    def floats_settle(self, fid: int):
+        """Takes the record that an advance of a migrating set deferred."""
+        self._check(lib().hnumo_floats_settle(self.h, int(fid)))
+
     def bench_steps(self, nsteps: int):
         t = C.c_double()
         k = C.c_double()
@@ -619,3 +658,19 @@ def group_ti_rk_bcl(engines, states):
     if rc:
         msgs = [lib().hnumo_last_error(e.h).decode() for e in engines]
         raise EngineError(rc, "; ".join(m for m in msgs if m))
+
+
+def _group_check(engines, rc):
+    if rc:
+        msgs = [lib().hnumo_last_error(e.h).decode() for e in engines]
+        raise EngineError(rc, "; ".join(m for m in msgs if m))
+
+
+def group_floats_migrate(engines, fid: int, on: bool = True, coord_scale: float = 0.0):
+    """hnumo_floats_migrate on every engine of a local group; a seed ACTIVE on several ranks stays on the lowest."""
+    _group_check(engines, lib().hnumo_group_floats_migrate(engines[0]._group, len(engines), int(fid), int(bool(on)), float(coord_scale)))
+
+
+def group_floats_advance(engines, fid: int, dt: float):
+    """One advance by dt of the migrating set fid on every engine of a local group, and its arrivals."""
+    _group_check(engines, lib().hnumo_group_floats_advance(engines[0]._group, len(engines), int(fid), float(dt)))

@@ -32,7 +32,16 @@ advance(dt): Heun with the field of the new time level (w is from the previous o
     non-finite velocity gives LOST likewise at the target located last.  Inactive floats never change.
 
 The two classes agree bit for bit (tests/test_floats_gpu.py), and with the C++ host statement
-(tests/test_float_plan.py)."""
+(tests/test_float_plan.py).
+
+Migration (processor-face ranks, opt-in; include/hnumo_engine.h has the normative text): in a migrating set
+a location that reaches (3) at a processor face puts the float in flight instead of LEFT; the rank across
+the face resumes the advance at the statement where it stopped, so a float's record on the rank that
+holds it is the single-rank float's, bit for bit, through any number of crossings.
+
+    HostFloatGroup      the numpy mirror of the group protocol over one HostFloats per rank
+    GroupFloats         the same set on the engines of a local group (hnumo_group_floats_*)
+    merge_series        the ranks' series as one, with global element numbers"""
 from __future__ import annotations
 
 import math
@@ -42,6 +51,8 @@ import numpy as np
 from . import sample as _sample
 
 ACTIVE, LEFT, LOST = 0, 1, 2      # HNUMO_FLOAT_ACTIVE, HNUMO_FLOAT_LEFT, HNUMO_FLOAT_LOST
+FLIGHT = 3                        # locate's answer at a processor face of a migrating set (never a float's status)
+MAXROUNDS = 8                     # rounds of arrivals that settle one advance
 WALL, OFF_RANK = -1, -2           # side neighbours that are no element
 SIDES = ("xi=-1", "xi=+1", "eta=-1", "eta=+1")
 EPS = 2.0 ** -52
@@ -131,7 +142,7 @@ class HostFloats:
 
     needs_host_state = True
 
-    def __init__(self, case, xy, layer, xgl=None, coord=None):
+    def __init__(self, case, xy, layer, xgl=None, coord=None, coord_scale=0.0):
         S = case.scalars
         self.case = case
         self.ngl, self.L, self.npoin = S["ngl"], S["nlayers"], S["npoin"]
@@ -155,7 +166,20 @@ class HostFloats:
         self._lo = c.min(axis=2) if self.ne else np.zeros((2, 0))
         self._hi = c.max(axis=2) if self.ne else np.zeros((2, 0))
         self._records = []
+        self.xface = None                 # a migrating set's side table (migrate_tables), else None
+        self.outbox = []                  # its flight records since it was last emptied
         self.set(xy, layer)
+        if coord_scale:
+            self.set_coord_scale(coord_scale)
+
+    def set_coord_scale(self, scale):
+        """tol_e of every later location from max|coord| = scale (0: the case's own again); seeds stay."""
+        if not (scale >= 0.0 and math.isfinite(scale)):
+            raise ValueError("coord_scale must be finite and >= 0")
+        ex = np.roll(self.corners.reshape(self.ne, 4, 2), -1, axis=1) - self.corners.reshape(self.ne, 4, 2)
+        edge = np.sqrt(ex[:, :, 0] * ex[:, :, 0] + ex[:, :, 1] * ex[:, :, 1])
+        self.tol = (64.0 * EPS * (scale if scale > 0.0 else self.maxc)) / (0.5 * edge.min(axis=1))
+        self._tol = [float(v) for v in self.tol]
 
     # ---- seeding
     def set(self, xy, layer):
@@ -219,10 +243,10 @@ class HostFloats:
             v = ly[0] * rv if j == 0 else v + ly[j] * rv
         return u, v
 
-    def locate(self, px, py, e):
+    def locate(self, px, py, e, hops=0):
         """(status, e, xi, eta, px, py, hops): the location of the target (px, py) starting from the
-        0-based element e."""
-        hops = 0
+        0-based element e with `hops` passes through (3) behind it.  In a migrating set a processor face
+        gives FLIGHT, and self._dest = (k, pos)."""
         xi = eta = 0.0
         while True:
             c = self._c[e]
@@ -251,12 +275,58 @@ class HostFloats:
                 px, py = x
                 self.walls += 1
             else:
+                if self.xface is not None:
+                    k, pos = self.xface[e][(2 if in_eta else 0) + (1 if plus else 0)]
+                    if k >= 0:
+                        self._dest = (k, pos)
+                        return FLIGHT, e, xi, eta, px, py, hops
                 return LEFT, e, xi, eta, px, py, hops
 
     def _stop(self, m, status, px, py):
         self.status[m], self.x[m], self.y[m] = status, px, py
         self.elem[m] = 0
         self.wx[m] = self.wy[m] = 0.0
+
+    def _heun(self, q, k, x, y, wx, wy, dt, stage, px, py, e, hops):
+        """The advance of (x, y, w) in layer k (0-based) from a stage on (float_plan.h: float_heun): stage 0
+        locates p* = (px, py) from e, u* = vel, p1, and goes on as stage 1 with no pass behind it; stage 1
+        locates p1 = (px, py), w = vel.  Returns (status, e, xi, eta, px, py, us, vs, stage, hops of the
+        last location, most hops of a location)."""
+        us = vs = 0.0
+        most = 0
+        if stage == 0:
+            st, e, xi, eta, px, py, h = self.locate(px, py, e, hops)
+            most = h
+            if st == ACTIVE:
+                us, vs = self.vel(q, k, e, xi, eta)
+                if not (math.isfinite(us) and math.isfinite(vs)):
+                    st = LOST
+            if st != ACTIVE:
+                return st, e, xi, eta, px, py, us, vs, 0, h, most
+            px, py = x + (0.5 * dt) * (wx + us), y + (0.5 * dt) * (wy + vs)
+            hops = 0
+        st, e, xi, eta, px, py, h = self.locate(px, py, e, hops)
+        if st == ACTIVE:
+            us, vs = self.vel(q, k, e, xi, eta)
+            if not (math.isfinite(us) and math.isfinite(vs)):
+                st = LOST
+        return st, e, xi, eta, px, py, us, vs, 1, h, max(most, h)
+
+    def _finish(self, m, res, k, x, y, wx, wy, dt):
+        """Float m after _heun: it moved, it stopped, or it is in flight (its slot LEFT, a record in the outbox)."""
+        st, e, xi, eta, px, py, us, vs, stage, h, most = res
+        self.hops[m] = max(self.hops[m], most)
+        self.walled[m] = self.walled[m] or self.walls > 0
+        if st == FLIGHT:
+            self.outbox.append(dict(gid=m, layer=k + 1, x=x, y=y, wx=wx, wy=wy, dt=dt, stage=stage, px=px, py=py, hops=h,
+                                    k=self._dest[0], pos=self._dest[1]))
+            st = LEFT
+        if st != ACTIVE:
+            self._stop(m, st, px, py)
+            return
+        self.status[m] = ACTIVE           # (an arrival's slot was LEFT)
+        self.x[m], self.y[m], self.wx[m], self.wy[m] = px, py, us, vs
+        self.elem[m], self.xi[m], self.eta[m] = e + 1, xi, eta
 
     def advance(self, q_df, dt=None):
         """One advance of every ACTIVE float by dt (default: the case's dt) on q_df (3, npoin, L).
@@ -280,25 +350,26 @@ class HostFloats:
                     self._stop(m, LOST, x, y)
                     continue
             wx, wy = float(self.wx[m]), float(self.wy[m])
-            st, e, xi, eta, px, py, h1 = self.locate(x + dt * wx, y + dt * wy, e)
-            self.hops[m] = h1
-            if st == ACTIVE:
-                us, vs = self.vel(q, k, e, xi, eta)
-                if not (math.isfinite(us) and math.isfinite(vs)):
-                    st = LOST
-            if st == ACTIVE:
-                st, e, xi, eta, px, py, h2 = self.locate(x + (0.5 * dt) * (wx + us), y + (0.5 * dt) * (wy + vs), e)
-                self.hops[m] = max(h1, h2)
-            if st == ACTIVE:
-                us, vs = self.vel(q, k, e, xi, eta)
-                if not (math.isfinite(us) and math.isfinite(vs)):
-                    st = LOST
-            self.walled[m] = self.walls > 0
-            if st != ACTIVE:
-                self._stop(m, st, px, py)
-                continue
-            self.x[m], self.y[m], self.wx[m], self.wy[m] = px, py, us, vs
-            self.elem[m], self.xi[m], self.eta[m] = e + 1, xi, eta
+            self._finish(m, self._heun(q, k, x, y, wx, wy, dt, 0, x + dt * wx, y + dt * wy, e, 0), k, x, y, wx, wy, dt)
+
+    def resume(self, q_df, fl, e):
+        """The tail of an advance from the flight record fl (a dict as in outbox) in this rank's 0-based
+        element e behind the face: float_plan.h's float_resume, into slot fl["gid"]."""
+        m, k = fl["gid"], fl["layer"] - 1
+        self.walls = 0
+        self._through = self.visited[m]
+        self.fresh[m] = 0
+        res = self._heun(np.asarray(q_df), k, fl["x"], fl["y"], fl["wx"], fl["wy"], fl["dt"], fl["stage"], fl["px"], fl["py"], e,
+                         fl["hops"])
+        self._finish(m, res, k, fl["x"], fl["y"], fl["wx"], fl["wy"], fl["dt"])
+
+    def release(self, idx):
+        """The floats idx that are ACTIVE here become LEFT, elem 0, w 0 (hnumo_floats_release)."""
+        for m in idx:
+            if self.status[m] == ACTIVE:
+                self.status[m], self.elem[m] = LEFT, 0
+                self.wx[m] = self.wy[m] = 0.0
+                self.visited[m] = set()
 
     after_step = advance
 
@@ -371,6 +442,173 @@ class DeviceFloats:
 
     def destroy(self):
         self.engine.floats_destroy(self.id)
+
+
+def migrate_tables(part):
+    """(xface (ne, 4, 2) int32, arrive [per neighbour: 0-based elements]) of a processor-face rank: the side
+    of face(7) that the face at position pos of neighbour k's list lies on gets (k, pos), every other side
+    (-1, -1); arrive[k][pos] is that element."""
+    A, ngl = part.arrays, part.scalars["ngl"]
+    face, imapl = np.asarray(A["face"]), np.asarray(A["imapl"])
+    ne = _sample.owned_elements(part)
+    xface = np.full((ne, 4, 2), -1, dtype=np.int32)
+    arrive = []
+    for k, nb in enumerate(part.fneighbours):
+        els = []
+        for pos, f in enumerate(nb.faces):
+            f = int(f)
+            el = int(face[6, f])
+            if face[7, f] != 0 or not 1 <= el <= ne:
+                raise ValueError(f"face {f + 1} is not a processor face of an owned element")
+            i, j = imapl[0, :, f], imapl[1, :, f]
+            on = [(i == 1).all(), (i == ngl).all(), (j == 1).all(), (j == ngl).all()]
+            if sum(on) != 1:
+                raise ValueError(f"face {f + 1}: its nodes are not one side of element {el}")
+            sd = on.index(True)
+            if xface[el - 1, sd, 0] >= 0:
+                raise ValueError(f"face {f + 1} lies on a side that is listed already")
+            xface[el - 1, sd] = (k, pos)
+            els.append(el - 1)
+        arrive.append(els)
+    return xface, arrive
+
+
+class HostFloatGroup:
+    """The numpy mirror of a migrating set on the ranks `parts` (hnumo.facepart.face_partition cases, in rank
+    order): one HostFloats per rank, seeded from the same xy, layer; a seed ACTIVE on several ranks stays on
+    the lowest.  advance(states, dt) is hnumo_group_floats_advance on the ranks' synced states.  For the
+    tests it keeps, per float, crossings = [(advance, stage, hops, from rank, to rank), ...] and
+    path = the ranks that held it after each advance; rounds = the rounds the last advance took."""
+
+    def __init__(self, parts, xy, layer, coord_scale=0.0):
+        self.parts = list(parts)
+        self.ranks = [HostFloats(p, xy, layer, coord_scale=coord_scale) for p in self.parts]
+        self.M = self.ranks[0].M
+        self.arrive = []
+        for p, hf in zip(self.parts, self.ranks):
+            hf.xface, arr = migrate_tables(p)
+            hf.xface = [[(int(k), int(pos)) for k, pos in row] for row in hf.xface]
+            self.arrive.append(arr)
+        self.shared = np.sum([hf.status == ACTIVE for hf in self.ranks], axis=0) > 1
+        held = np.zeros(self.M, bool)
+        for hf in self.ranks:
+            on = hf.status == ACTIVE
+            hf.release(np.nonzero(on & held)[0])
+            held |= on
+        self.crossings = [[] for _ in range(self.M)]
+        self.path = [[r for r, hf in enumerate(self.ranks) if hf.status[m] == ACTIVE] for m in range(self.M)]
+        self.nadvance = self.rounds = self.max_rounds = 0
+        self.in_flight_after = 0
+
+    def neighbour_index(self, r, rank):
+        return [nb.rank for nb in self.parts[r].fneighbours].index(rank)
+
+    def advance(self, states, dt=None):
+        for hf, q in zip(self.ranks, states):
+            hf.outbox = []
+            hf.advance(q, dt)
+        hops = [hf.hops.copy() for hf in self.ranks]
+        walled = [hf.walled.copy() for hf in self.ranks]
+        self.rounds = 0
+        for rnd in range(MAXROUNDS + 1):
+            boxes = [hf.outbox for hf in self.ranks]
+            if not any(boxes):
+                break
+            if rnd == MAXROUNDS:
+                for hf, box in zip(self.ranks, boxes):      # (cannot happen) still in flight: LOST where it left
+                    for fl in box:
+                        hf.status[fl["gid"]] = LOST
+                self.in_flight_after += sum(len(b) for b in boxes)
+                break
+            self.rounds = rnd + 1
+            for hf in self.ranks:
+                hf.outbox = []
+            for r, hf in enumerate(self.ranks):
+                for k, nb in enumerate(self.parts[r].fneighbours):
+                    me = self.neighbour_index(nb.rank, r)
+                    for fl in sorted(boxes[nb.rank], key=lambda f: f["gid"]):
+                        if fl["k"] != me:
+                            continue
+                        self.crossings[fl["gid"]].append((self.nadvance, fl["stage"], fl["hops"], nb.rank, r))
+                        hf.resume(states[r], fl, self.arrive[r][k][fl["pos"]])
+        for r, hf in enumerate(self.ranks):
+            hf.hops, hf.walled = np.maximum(hf.hops, hops[r]), hf.walled | walled[r]
+        self.max_rounds = max(self.max_rounds, self.rounds)
+        self.nadvance += 1
+        for m in range(self.M):
+            on = [r for r, hf in enumerate(self.ranks) if hf.status[m] == ACTIVE]
+            assert len(on) <= 1, (m, on)
+            if on and (not self.path[m] or self.path[m][-1] != on[0]):
+                self.path[m].append(on[0])
+
+    def get(self):
+        return [hf.get() for hf in self.ranks]
+
+    def record(self):
+        for hf in self.ranks:
+            hf.record()
+
+    def series(self, clear: bool = False):
+        return [hf.series(clear) for hf in self.ranks]
+
+
+def merge_series(series_per_rank, parts):
+    """(5, M, count) from the ranks' series (5, M, count) of one migrating set: for each float and record the
+    rank where elem > 0, its element numbered globally (1-based, through parts[r].elems).  A float no rank
+    holds in a record (it left the domain's ranks, or is LOST) is taken from the rank that held it last, from
+    rank 0 if none ever did."""
+    sers = [np.asarray(s) for s in series_per_rank]
+    out = np.array(sers[0], order="F", copy=True)
+    _, M, count = out.shape
+    last = np.zeros(M, dtype=np.int64)
+    for i in range(count):
+        held = np.zeros(M, bool)
+        for r, (ser, p) in enumerate(zip(sers, parts)):
+            on = ser[4, :, i] > 0
+            if (on & held).any():
+                raise ValueError(f"record {i}: a float has elem > 0 on two ranks")
+            held |= on
+            last[on] = r
+        for r, (ser, p) in enumerate(zip(sers, parts)):
+            take = last == r
+            glob = np.concatenate([[0], np.asarray(p.elems[:_sample.owned_elements(p)]) + 1]).astype(np.float64)
+            out[:, take, i] = ser[:, take, i]
+            out[4, take, i] = glob[ser[4, take, i].astype(np.int64)]
+    return out
+
+
+class GroupFloats:
+    """A migrating float set on the engines of a local group (processor-face ranks, in rank order): the same
+    xy, layer on every engine, hnumo_group_floats_migrate, and then begin / advance / get / series / destroy;
+    get() and series() return one entry per rank (merge_series joins the series)."""
+
+    def __init__(self, engines, xy, layer, coord_scale=0.0, migrate=True):
+        from .engine import group_floats_migrate
+        self.engines = list(engines)
+        self.sets = [DeviceFloats(e, xy, layer) for e in self.engines]
+        self.id = self.sets[0].id
+        if any(s.id != self.id for s in self.sets):
+            raise ValueError("the set must get the same id on every engine of the group")
+        if migrate:
+            group_floats_migrate(self.engines, self.id, True, coord_scale)
+
+    def begin(self, every: int = 1, record_every: int = 0, capacity: int = 0):
+        for s in self.sets:
+            s.begin(every, record_every, capacity)
+
+    def advance(self, dt=None):
+        from .engine import group_floats_advance
+        group_floats_advance(self.engines, self.id, self.engines[0].case.scalars["dt"] if dt is None else dt)
+
+    def get(self):
+        return [s.get() for s in self.sets]
+
+    def series(self, clear: bool = False):
+        return [s.series(clear) for s in self.sets]
+
+    def destroy(self):
+        for s in self.sets:
+            s.destroy()
 
 
 def seed_grid(case, nx: int, ny: int, margin: float = 0.05):

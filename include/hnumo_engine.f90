@@ -90,7 +90,8 @@ module hnumo_engine_c
         hnumo_sample_create, hnumo_sample_create_ref, hnumo_sample_plan, hnumo_sample, &
         hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy, &
         hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
-        hnumo_floats_begin, hnumo_floats_record, hnumo_floats_series, hnumo_floats_destroy
+        hnumo_floats_begin, hnumo_floats_record, hnumo_floats_series, hnumo_floats_destroy, &
+        hnumo_floats_migrate, hnumo_floats_release, hnumo_floats_outbox, hnumo_floats_deliver, hnumo_floats_settle
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
     integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1, &
         HNUMO_SAMPLE_VORT = 2   ! sample set sources
@@ -500,6 +501,50 @@ module hnumo_engine_c
             type(c_ptr), value :: eng
             integer(c_int32_t), value :: id
         end function hnumo_floats_destroy
+
+        ! migrating sets (processor-face ranks): on = 1 hands floats that reach a processor face to the rank
+        ! across it; coord_scale > 0 replaces the rank's max|coord| in tol_e
+        integer(c_int) function hnumo_floats_migrate(eng, id, on, coord_scale) bind(C, name='hnumo_floats_migrate')
+            import :: c_int, c_int32_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id, on
+            real(c_double), value :: coord_scale
+        end function hnumo_floats_migrate
+
+        ! floats idx(n) (0-based input positions) that are ACTIVE on this rank become LEFT
+        integer(c_int) function hnumo_floats_release(eng, id, idx, n) bind(C, name='hnumo_floats_release')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            integer(c_int32_t), intent(in) :: idx(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_floats_release
+
+        ! d(cap,7) = x, y, wx, wy, dt, px, py; i(cap,6) = gid, layer, stage, hops, dest (0-based rank), pos
+        integer(c_int) function hnumo_floats_outbox(eng, id, d, i, cap, count) bind(C, name='hnumo_floats_outbox')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(out) :: d(*)
+            integer(c_int32_t), intent(out) :: i(*)
+            integer(c_int64_t), value :: cap
+            integer(c_int64_t), intent(out) :: count
+        end function hnumo_floats_outbox
+
+        integer(c_int) function hnumo_floats_deliver(eng, id, src_rank, d, i, cap, n) bind(C, name='hnumo_floats_deliver')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id, src_rank
+            real(c_double), intent(in) :: d(*)
+            integer(c_int32_t), intent(in) :: i(*)
+            integer(c_int64_t), value :: cap, n
+        end function hnumo_floats_deliver
+
+        integer(c_int) function hnumo_floats_settle(eng, id) bind(C, name='hnumo_floats_settle')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+        end function hnumo_floats_settle
     end interface
 
 contains

@@ -434,8 +434,63 @@ int hnumo_sample_destroy(hnumo_engine *eng, int32_t id);
  *     w = vel(e1, xi1, eta1);  (x, y) = p1;  (elem, xi, eta) = (e1, xi1, eta1)
  *     A location that ends LEFT or LOST stops the advance: (x, y) = that location's target, elem = 0,
  *     w = 0; a non-finite velocity gives LOST likewise, at the target located last.  Inactive floats
- *     are never touched again.  Moving a LEFT float to the neighbouring rank is the host's job
- *     (hnumo_floats_get there, hnumo_floats_set / _create here).
+ *     are never touched again.  On a processor-face partition a set that migrates (below) hands a
+ *     float that reaches a processor face to the rank across it, inside the engine.
+ *
+ * Migration (hnumo_floats_migrate; processor-face engines, opt-in; a set that does not opt in is as above).
+ *   Flight record.  When locate reaches (3) at a processor face (face(8) = 0) in a migrating set, the
+ *     float is in flight instead of LEFT.  Its record carries: gid, its 0-based input index (every rank
+ *     creates the set from the same xy(2,M), layer(M)); layer; the position (x, y) and velocity (wx, wy)
+ *     it had at the start of this advance (after the fresh evaluation); dt; stage (0 while locating p*,
+ *     1 while locating p1); the current target (px, py), as walls may have moved it; hops, the passes
+ *     through (3) so far in this location, counting the one that reached the face; the destination:
+ *     the neighbour index k in this rank's nbh_proc and the position pos of the face inside that
+ *     neighbour's segment of nbh_send_recv (both ranks agree on that order: the halo descriptor's
+ *     contract).
+ *   Arrival.  The receiver's face at (its neighbour index for the sender, pos) gives the local element
+ *     face(7).  locate continues there at (1) with the carried target and hop count; the advance goes
+ *     on from the carried stage with the statements of advance -- stage 0: u* = vel, p1, a second
+ *     location starting with hops = 0, w = vel; stage 1: w = vel.  The result goes into the receiver's
+ *     own slot gid, which is LEFT there by construction.
+ *   Sender's slot.  LEFT exactly as without migration: (x, y) = the target, elem = 0, w = 0.
+ *   Further crossings.  A continuation may reach another processor face: another flight.  Every flight
+ *     uses up at least one hop and a location allows four, so an advance settles in at most 8 rounds
+ *     of arrivals; the round loop has that bound, and a float still in flight after round 8 is LOST
+ *     where it left (this cannot happen).
+ *   Tolerance.  tol_e depends on max|coord|, which a rank takes over its own nodes.  coord_scale > 0
+ *     replaces it in tol_e for every later location of the set, so that all ranks and the single-rank
+ *     run accept on the same threshold; 0 keeps the rank's own.  Seeds are not re-located.
+ *   Seeds on shared edges.  A seed on an edge two ranks share is ACTIVE on both at creation; in a
+ *     migrating set a float may be ACTIVE on one rank only.  hnumo_group_floats_migrate keeps it on the
+ *     lowest rank that holds it and makes it LEFT (elem 0, w 0) on the others; hnumo_floats_release does
+ *     the same for a host that transports the records itself.
+ *   Per record at most one rank has elem > 0 for a float; that rank's record is the single-rank float's,
+ *   bit for bit, through any number of crossings (with one coord_scale everywhere).
+ *
+ * hnumo_floats_migrate: on = 1 / 0, coord_scale as above.  4 on an engine without a processor-face halo
+ *   (a single rank, a ghost-layer partition, the self-neighbour emulation), for a negative or non-finite
+ *   scale, for an unknown id.  hnumo_floats_set on a migrating set re-seeds this rank alone.
+ * hnumo_group_floats_migrate: the same on every engine of a local group, plus the shared-edge rule.
+ * hnumo_group_floats_advance: every engine's advance of the set by dt, then rounds (at most 8, until no
+ *   float is in flight): synchronise every engine's stream, read back the outbox counts, run the
+ *   arrivals of every non-empty outbox on its receivers, flip the outboxes' parity.  The records that
+ *   fell due are taken on every engine after the last round.  hnumo_group_ti_rk_bcl runs the same
+ *   phase with params.dt for every migrating set with every = 1, after all engines' other observers:
+ *   floats are still last, a refused recording still lets everything else run, and the first non-zero
+ *   code is returned.
+ * For a host that carries the records itself (one engine per process, MPI or RCCL between the GPUs;
+ * transport of flight records over RCCL inside the engine is out of scope, these calls are its
+ * interface): on such an engine an advance of a migrating set, explicit or after a step, defers the
+ * record that falls due to hnumo_floats_settle.
+ *   hnumo_floats_outbox: the flight records of the current outbox into d(cap,7) = x, y, wx, wy, dt, px,
+ *     py and i(cap,6) = gid, layer, stage, hops, dest, pos, sorted by gid; dest is the destination's
+ *     0-based rank (nbh_proc(k) - 1); *count of them.  The outbox is then empty: flights of later
+ *     arrivals collect in it.  cap < count: 4, nothing taken.
+ *   hnumo_floats_deliver: runs the arrivals of the n records that rank src_rank sent (those whose dest
+ *     is another rank are dropped).  4 for a rank that shares no face with this one and for a record
+ *     whose gid, layer, stage, hops or pos no sender produces.
+ *   hnumo_floats_release: floats idx(n) (0-based input positions) that are ACTIVE here become LEFT.
+ *   hnumo_floats_settle: takes the record that the advance deferred (none: nothing happens).
  *
  * hnumo_floats_create: coord(ldc,npoin), xgl(ngl) as hnumo_sample_create takes them (the same element
  *   contract and initial location); xy(2,M), layer(M) in 1..nlayers.  Returns the set's id (0..7: up to
@@ -477,6 +532,12 @@ int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t rec
 int hnumo_floats_record(hnumo_engine *eng, int32_t id);
 int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear);
 int hnumo_floats_destroy(hnumo_engine *eng, int32_t id);
+int hnumo_floats_migrate(hnumo_engine *eng, int32_t id, int32_t on, double coord_scale);
+int hnumo_floats_release(hnumo_engine *eng, int32_t id, const int32_t *idx, int64_t n);
+int hnumo_floats_outbox(hnumo_engine *eng, int32_t id, double *d, int32_t *i, int64_t cap, int64_t *count);
+int hnumo_floats_deliver(hnumo_engine *eng, int32_t id, int32_t src_rank, const double *d, const int32_t *i, int64_t cap,
+                         int64_t n);
+int hnumo_floats_settle(hnumo_engine *eng, int32_t id);
 
 /* Summation order of the barotropic stage (no reference counterpart: the reference has
  * one order).  HNUMO_SUM_REFERENCE (the default) evaluates the volume integral and the
@@ -539,6 +600,9 @@ int hnumo_rccl_unique_id(unsigned char *out128);
  * (one host thread per engine).  For tests of the multi-rank path on one GPU.        */
 int hnumo_local_group(hnumo_engine **engines, int n);
 int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double **qb_df, double **qprime_df);
+/* migrating float sets of a local group (see the float sets above); engines: the group's, in rank order */
+int hnumo_group_floats_migrate(hnumo_engine **engines, int n, int32_t id, int32_t on, double coord_scale);
+int hnumo_group_floats_advance(hnumo_engine **engines, int n, int32_t id, double dt);
 
 /* Timing hook for the benchmark: run `nsteps` resident baroclinic steps and return
  * device-side event timings (ms) of the whole span and of the dominant kernel.       */
