@@ -331,6 +331,13 @@ static void face_exchange_cdef(hnumo_engine *e);
 // by the face kernels before them.  Multi-rank engines run the extract launches and face kernels.
 static bool fused_extract(const hnumo_engine *e) { return e->comm_mode == 0 && e->nranks == 1 && !e->face_halo; }
 
+// the LEAN arena Launch::stage launches for this engine (StageCfg NBK workgroups per CU: 4 or 5;
+// HNUMO_STAGE_NB), 0: the arena of small meshes -- N = 4 in the reference summation order only
+// (hnumo_kernel_variants reports it)
+static int stage_arena(const hnumo_engine *e) {
+  return e->ngl == 5 && e->summation == HNUMO_SUM_REFERENCE && (e->stage_nb == 4 || e->stage_nb == 5) ? e->stage_nb : 0;
+}
+
 template <int NGL, int NQ>
 struct Launch {
   static constexpr int BSE = ((NQ * NQ + 63) / 64) * 64;
@@ -346,9 +353,9 @@ struct Launch {
       return;
     }
     if constexpr (NGL == 5) {
-      // the LEAN arenas of large meshes (StageCfg NBK workgroups per CU; HNUMO_STAGE_NB)
-      if (e->summation == HNUMO_SUM_REFERENCE && (e->stage_nb == 4 || e->stage_nb == 5)) {
-        if (e->stage_nb == 5)
+      // the LEAN arenas of large meshes
+      if (const int nb = stage_arena(e)) {
+        if (nb == 5)
           launch_nb<5>(n, st, stop, a);
         else
           launch_nb<4>(n, st, stop, a);
@@ -1690,6 +1697,13 @@ int hnumo_set_summation(hnumo_engine *eng, int mode) {
 int hnumo_get_summation(hnumo_engine *eng) { return eng ? eng->summation : -1; }
 
 int hnumo_stage_path(hnumo_engine *eng) { return eng ? (use_persistent(eng) ? 1 : 0) : -1; }
+
+int hnumo_kernel_variants(hnumo_engine *eng, int32_t out[2]) {
+  if (!eng || !out) return HNUMO_ERR_INVALID;
+  out[0] = stage_arena(eng);
+  out[1] = eng->bcl_big ? 1 : 0;
+  return 0;
+}
 
 extern "C++" template <int NGL, int NQ>
 static int subcycle_lds_bytes(const hnumo_engine *e) {

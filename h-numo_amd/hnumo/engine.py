@@ -59,6 +59,7 @@ def lib():
         L.hnumo_get_summation.restype = C.c_int
         L.hnumo_stage_path.argtypes = [vp]
         L.hnumo_stage_path.restype = C.c_int
+        L.hnumo_kernel_variants.argtypes = [vp, C.POINTER(C.c_int32)]
         L.hnumo_persistent_info.argtypes = [vp, C.POINTER(C.c_int32)]
         L.hnumo_persistent_stats.argtypes = [vp, C.POINTER(C.c_int32)]
         L.hnumo_debug_force_abort.argtypes = [vp, C.c_int]
@@ -233,6 +234,16 @@ class Engine:
     def stage_path(self) -> str:
         """'persistent' (one launch per sub-cycle) or 'per-stage' (one launch per stage)."""
         return "persistent" if lib().hnumo_stage_path(self.h) == 1 else "per-stage"
+
+    @property
+    def kernel_variants(self) -> dict:
+        """The device code variants this engine launches (hnumo_kernel_variants): stage_arena, the
+        per-stage barotropic kernel's LDS arena (5 or 4: a LEAN arena of large meshes, 0: the
+        small-mesh arena, and always 0 unless N = 4 in the reference summation order), and bcl_big,
+        whether the layer mass / consistency kernels are the large-mesh ones."""
+        out = (C.c_int32 * 2)()
+        self._check(lib().hnumo_kernel_variants(self.h, out))
+        return dict(stage_arena=int(out[0]), bcl_big=bool(out[1]))
 
     @property
     def persistent_info(self) -> dict:

@@ -83,6 +83,7 @@ module hnumo_engine_c
         hnumo_ti_barotropic_ssprk, hnumo_btp_bcl_coeffs, hnumo_create_rhs_btp, hnumo_get_field_c, &
         hnumo_set_resident, hnumo_sync, hnumo_last_error_c, hnumo_last_error, hnumo_get_field, &
         hnumo_set_summation, hnumo_get_summation, hnumo_stage_path, hnumo_persistent_info, hnumo_predict, &
+        hnumo_kernel_variants, &
         hnumo_rccl_unique_id, hnumo_persistent_stats, hnumo_diag_geometry, hnumo_diagnostics, &
         hnumo_layer_fields, hnumo_stats_begin, hnumo_stats_accumulate, hnumo_stats_sums, &
         hnumo_stats_set_sums, hnumo_stats_fields, hnumo_stats_series, hnumo_stats_end, &
@@ -192,6 +193,14 @@ module hnumo_engine_c
             import :: c_int, c_ptr
             type(c_ptr), value :: eng
         end function hnumo_stage_path
+
+        ! the device code variants launched, out(2) = (stage kernel arena 0 | 4 | 5, large-mesh
+        ! mass / consistency kernels 0 | 1): see hnumo_engine.h
+        integer(c_int) function hnumo_kernel_variants(eng, out) bind(C, name='hnumo_kernel_variants')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), intent(out) :: out(2)
+        end function hnumo_kernel_variants
 
         ! residency of the persistent launch, out(8): see hnumo_engine.h
         integer(c_int) function hnumo_persistent_info(eng, out) bind(C, name='hnumo_persistent_info')

@@ -560,6 +560,14 @@ int hnumo_get_summation(hnumo_engine *eng);
  * Both give the same bits.                                                            */
 int hnumo_stage_path(hnumo_engine *eng);
 
+/* Which variants of the device code this engine launches (additive in ABI v10; no device work).
+ * out[0]: the LDS arena of the per-stage barotropic kernel -- 5 or 4: a LEAN arena of large meshes
+ * (the default from 2,048 owned elements on: 5), 0: the arena of small meshes; always 0 unless
+ * N = 4 and the summation is HNUMO_SUM_REFERENCE, where the kernel has one arena.  out[1]: 1 when
+ * the layer mass / consistency element kernels are the large-mesh ones (one quad row per term
+ * chunk; the default from 2,048 owned elements on), else 0.  All variants give the same bits. */
+int hnumo_kernel_variants(hnumo_engine *eng, int32_t out[2]);
+
 /* Residency of the persistent sub-cycle launch (ABI v6).  The launch is used only when
  * every element's workgroup can be resident at once: the occupancy estimate says so, a
  * stage-less trial launch at create finds all workgroups resident, and every launch

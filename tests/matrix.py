@@ -12,6 +12,13 @@ CELLS is chosen so that every pair of levels of (N x each other factor) and of (
 each other factor) occurs, and so that the N = 7 rows and the single-layer rows together see
 every level of every other factor; tests/test_states_cpu.py asserts both, so that an edit cannot
 quietly thin the list.
+
+VARIANTS names the device code that an engine of 2,048 owned elements or more switches to (engine.hip,
+read_knobs): the LEAN arenas of the per-stage barotropic kernel (N = 4 only) and the large-mesh layer
+mass / consistency kernels (every N).  Neither depends on the mesh size in anything but that choice,
+so the experiment knobs force them onto the cells' 16 or 9 elements, and the cells' own oracle
+results judge them.  The N = 4 rows -- all that the LEAN arenas can see -- must by themselves hold
+every level of every other factor (test_states_cpu.py again).
 """
 import math
 
@@ -87,9 +94,43 @@ def _cells():
 
 CELLS = _cells()
 BY_NAME = {c["name"]: c for c in CELLS}
-# the processor-face halo on a moving state (brick cells): N = 7 with L = 1, N = 2, L = 1 at N = 4
+# the processor-face halo on a moving state (brick cells without the shear solve): N = 7 with L = 1, N = 2,
+# L = 1 at N = 4, three layers at N = 3, N = 5
 HALO_CELLS = ("N7-lake1-v1-noslip-b2-s0-brick-moving", "N2-lake2-v1-mixed-b1-s0-brick-moving",
-              "N4-lake1-v3-mixed-b1-s0-brick-moving")
+              "N4-lake1-v3-mixed-b1-s0-brick-moving", "N3-lake3-v0-mixed-b1-s0-brick-moving",
+              "N5-lake2-v1-mixed-b1-s0-brick-moving")
+
+
+# kernel variant -> (the environment that forces it at engine creation, the orders N it applies to)
+_LARGE = dict(HNUMO_EXPERIMENTS="1", HNUMO_PERSISTENT="0", HNUMO_STAGE_NB="5", HNUMO_BCL_BIG="1")
+VARIANTS = {
+    # what a mesh of >= 2,048 owned elements runs: the 5-per-CU LEAN arena and the large-mesh mass / cons kernels
+    "large": (_LARGE, LEVELS["N"]),
+    # the 4-per-CU LEAN arena; the arena knob has no effect but at N = 4, so elsewhere this would repeat "large"
+    "large-nb4": (dict(_LARGE, HNUMO_STAGE_NB="4"), (4,)),
+}
+
+
+def variant_cells(variant):
+    """The cells a kernel variant applies to."""
+    return [c for c in CELLS if c["N"] in VARIANTS[variant][1]]
+
+
+def variant_env(variant):
+    return dict(VARIANTS[variant][0])
+
+
+def variant_overrides(variant):
+    """What Engine.overrides lists under a variant: the honoured settings in the order the engine reads them
+    (HNUMO_EXPERIMENTS is the gate, not a setting)."""
+    env = VARIANTS[variant][0]
+    return [k + "=" + env[k] for k in ("HNUMO_STAGE_NB", "HNUMO_BCL_BIG", "HNUMO_PERSISTENT")]
+
+
+def variant_kernels(variant, N):
+    """Engine.kernel_variants of an order-N engine under a variant: the arena only where N = 4 has one."""
+    env = VARIANTS[variant][0]
+    return dict(stage_arena=int(env["HNUMO_STAGE_NB"]) if N == 4 else 0, bcl_big=env["HNUMO_BCL_BIG"] == "1")
 
 
 def cell_config(cell):
@@ -142,6 +183,12 @@ def missing_levels(cells):
     """The levels of any factor that neither an N = 7 cell nor a single-layer cell has."""
     rows = [c for c in cells if c["N"] == 7 or c["family"] == "lake1"]
     return sorted(((f, l) for f in FACTORS for l in LEVELS[f] if not any(c[f] == l for c in rows)), key=str)
+
+
+def missing_levels_of(cells):
+    """The levels of any factor but N that no cell of ``cells`` has."""
+    return sorted(((f, l) for f in FACTORS if f != "N" for l in LEVELS[f] if not any(c[f] == l for c in cells)),
+                  key=str)
 
 
 def run_oracle(case, nsteps):

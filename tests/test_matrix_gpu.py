@@ -4,17 +4,29 @@ viscosity methods, the wall codes, the drag laws, the shear solve and the mesh k
 that move (tests/states.py) -- on both stage paths, the default one and one launch per stage
 (HNUMO_PERSISTENT=0).  The oracle runs once per cell and is shared.
 
+Every cell runs again through the device code of large meshes (matrix.VARIANTS): an engine of 2,048
+owned elements or more launches the per-stage barotropic kernel in a LEAN arena (N = 4) and the
+large-mesh layer mass / consistency kernels (every N), which the cells' 16 or 9 elements would never
+reach.  The experiment knobs force them ("large": the 5-per-CU arena, all cells; "large-nb4": the
+4-per-CU arena, the N = 4 cells), every run asserts through Engine.kernel_variants that the variant
+is what launches, and the comparison is the same: the cell's oracle result, bit for bit.  The
+threshold itself is checked on engines that take no step.
+
 A cell with method_visc == 1 runs its Laplacian kernels between the stages, so its default path is
 the per-stage one (engine.hip, use_persistent); every other cell must take the persistent path.
 
 Per N, on a moving lake cell, the two halves of a step are compared on their own (create_rhs_btp
-and predict), which tells which half is wrong when a cell fails.  On the moving single-layer lake
-the resident engine's diagnostics, layer fields and flow statistics equal their host mirrors.
+and predict), on the default kernels and on the large-mesh ones, which tells which half is wrong
+when a cell fails: create_rhs_btp is the stage kernel alone, predict adds the mass / cons kernels.
+On the moving single-layer lake the resident engine's diagnostics, layer fields and flow statistics
+equal their host mirrors.
 
-The processor-face halo carries a moving state too: three cells (N = 7 with one layer, N = 2, one
-layer at N = 4) as 2-rank local groups against the reference Fortran under mpiexec on the same
-partitions (tests/golden/matrix_mpi2_*.npz), every rank bit for bit.  A 4x4 cell splits into two
-blocks; 3x3 elements do not, and split along the Morton curve."""
+The processor-face halo carries a moving state too: five cells (N = 7 with one layer, N = 2, one
+layer at N = 4, three layers at N = 3, N = 5) as 2-rank local groups against the reference Fortran
+under mpiexec on the same partitions (tests/golden/matrix_mpi2_*.npz), every rank bit for bit -- on
+the default kernels and on the large-mesh ones, which multi-rank engines run with the face kernels'
+fluxes and, in the LEAN arena, with the two-stream schedule's launches that signal their own stop
+event.  A 4x4 cell splits into two blocks; 3x3 elements do not, and split along the Morton curve."""
 import numpy as np
 import pytest
 
@@ -50,8 +62,41 @@ def first_difference(st, so, fields, ofields):
     return None
 
 
-@pytest.mark.parametrize("path", ["default", "per-stage"])
-@pytest.mark.parametrize("name", [c["name"] for c in M.CELLS])
+def variant_engines(variant, cases, monkeypatch):
+    """Engines of ``cases`` created under a kernel variant's environment (None: none), each checked
+    to launch that variant: the settings honoured, in the engine's order, and the kernels chosen."""
+    from hnumo.engine import Engine
+    env = M.variant_env(variant) if variant else {}
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    engines = []
+    try:
+        for c in cases:
+            engines.append(Engine(c))
+        for k in env:
+            monkeypatch.delenv(k)
+        for e in engines:
+            N = e.dims["ngl"] - 1
+            if variant:
+                assert e.overrides == M.variant_overrides(variant), e.overrides
+                assert not any("ignored" in x for x in e.overrides)
+                assert e.stage_path == "per-stage"
+                assert e.kernel_variants == M.variant_kernels(variant, N), (variant, N, e.kernel_variants)
+            else:
+                assert e.overrides == [] and e.kernel_variants == dict(stage_arena=0, bcl_big=False)
+    except BaseException:
+        for e in engines:
+            e.close()
+        raise
+    return engines
+
+
+# (name, path): every cell on the two stage paths and through the large-mesh kernel variants
+CELL_RUNS = [(c["name"], p) for c in M.CELLS for p in ("default", "per-stage")] + \
+            [(c["name"], v) for v in M.VARIANTS for c in M.variant_cells(v)]
+
+
+@pytest.mark.parametrize("name,path", CELL_RUNS, ids=["-".join(r) for r in CELL_RUNS])
 def test_cell_matches_oracle_bitwise(name, path, case_factory, monkeypatch):
     from hnumo import bundle as B
     from hnumo.engine import Engine
@@ -59,13 +104,18 @@ def test_cell_matches_oracle_bitwise(name, path, case_factory, monkeypatch):
     case = M.cell_case(cell, case_factory)
     so, ofields = oracle_of(cell, case)
     assert all(np.isfinite(x).all() for x in so)
-    if path == "per-stage":
-        monkeypatch.setenv("HNUMO_PERSISTENT", "0")
-    e = Engine(case)
-    monkeypatch.delenv("HNUMO_PERSISTENT", raising=False)
+    if path in M.VARIANTS:
+        e, = variant_engines(path, [case], monkeypatch)
+    else:
+        if path == "per-stage":
+            monkeypatch.setenv("HNUMO_PERSISTENT", "0")
+        e = Engine(case)
+        monkeypatch.delenv("HNUMO_PERSISTENT", raising=False)
     try:
-        want = "per-stage" if path == "per-stage" or cell["visc"] == 1 else "persistent"
+        want = "per-stage" if path != "default" or cell["visc"] == 1 else "persistent"
         assert e.stage_path == want, (e.stage_path, want)
+        if path == "default":
+            assert e.kernel_variants == dict(stage_arena=0, bcl_big=False)
         st = e.state()
         assert np.array_equal(st[0], case.arrays["q_df"])
         for _ in range(cell["nsteps"]):
@@ -81,14 +131,33 @@ def _moving_lake(N, family=None):
                 and (family is None or c["family"] == family))
 
 
-@pytest.mark.parametrize("N", M.LEVELS["N"])
-def test_step_halves_match_oracle_bitwise(N, case_factory):
-    """create_rhs_btp and predict on a moving lake cell of every N."""
-    import oracle as O
+@pytest.mark.parametrize("kw,want", [(dict(nelx=32, nely=64), (5, True)), (dict(nelx=23, nely=89), (0, False)),
+                                     (dict(nop=3, nelx=32, nely=64), (0, True))],
+                         ids=["2048", "2047", "2048-N3"])
+def test_large_mesh_kernels_start_at_2048_elements(kw, want, case_factory):
+    """The default choice at the threshold itself (engine.hip, read_knobs), on engines that take no step."""
     from hnumo.engine import Engine
+    case = case_factory("lake10", **kw)
+    assert case.scalars["nelem"] == kw["nelx"] * kw["nely"] and case.scalars["nelem"] in (2047, 2048)
+    e = Engine(case)
+    try:
+        assert e.overrides == []
+        assert e.kernel_variants == dict(stage_arena=want[0], bcl_big=want[1]), e.kernel_variants
+    finally:
+        e.close()
+
+
+HALF_RUNS = [(N, None) for N in M.LEVELS["N"]] + [(N, "large") for N in M.LEVELS["N"]]
+
+
+@pytest.mark.parametrize("N,variant", HALF_RUNS, ids=[str(N) + ("-" + v if v else "") for N, v in HALF_RUNS])
+def test_step_halves_match_oracle_bitwise(N, variant, case_factory, monkeypatch):
+    """create_rhs_btp and predict on a moving lake cell of every N, on the default kernels and the
+    large-mesh ones."""
+    import oracle as O
     case = M.cell_case(_moving_lake(N), case_factory)
     o = O.Oracle(case)
-    e = Engine(case)
+    e, = variant_engines(variant, [case], monkeypatch)
     try:
         q, qb, qp = o.state()
         o.btp_bcl_coeffs(qp)
@@ -147,14 +216,17 @@ def test_single_layer_diagnostics_and_statistics_equal_host(case_factory):
     assert np.array_equal(fields, hs.fields()) and np.array_equal(series, hs.series)
 
 
-@pytest.mark.parametrize("name", M.HALO_CELLS)
-def test_face_halo_moving_matches_reference_mpi(name):
+HALO_RUNS = [(n, None) for n in M.HALO_CELLS] + [(n, "large") for n in M.HALO_CELLS]
+
+
+@pytest.mark.parametrize("name,variant", HALO_RUNS, ids=[n + ("-" + v if v else "") for n, v in HALO_RUNS])
+def test_face_halo_moving_matches_reference_mpi(name, variant, monkeypatch):
     import json
     import os
     import states
     from util import overrides_of
     from hnumo.case import build_case, make_config
-    from hnumo.engine import Engine, group_ti_rk_bcl, local_group
+    from hnumo.engine import group_ti_rk_bcl, local_group
     from hnumo.facepart import face_partition
     gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "matrix_mpi2_" + name + ".npz")
     g = dict(np.load(gold, allow_pickle=False))
@@ -163,7 +235,7 @@ def test_face_halo_moving_matches_reference_mpi(name):
     R = int(g["nranks"])
     parts = [face_partition(case, R, r, str(g["order"])) for r in range(R)]
     assert all(not np.array_equal(p.arrays["q_df"][1], 0.0 * p.arrays["q_df"][1]) for p in parts)
-    engines = [Engine(p) for p in parts]
+    engines = variant_engines(variant, parts, monkeypatch)
     try:
         local_group(engines)
         sts = [e.state() for e in engines]

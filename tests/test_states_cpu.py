@@ -33,6 +33,26 @@ def test_matrix_covers_every_pair():
     assert sum(c["state"] == "rest" for c in M.CELLS) <= 6
 
 
+def test_kernel_variants_see_every_level():
+    """The LEAN arenas exist at N = 4 only, so the N = 4 rows are all that "large-nb4" (and the arena
+    of "large") can see: they hold every level of every other factor."""
+    assert set(M.VARIANTS) == {"large", "large-nb4"}
+    assert M.variant_cells("large") == M.CELLS
+    nb4 = M.variant_cells("large-nb4")
+    assert nb4 == [c for c in M.CELLS if c["N"] == 4] and len(nb4) >= 6
+    assert M.missing_levels_of(nb4) == []
+    # the assertion bites: a thinner list lacks a level
+    assert M.missing_levels_of([c for c in nb4 if c["state"] == "moving"])
+    assert M.missing_levels_of([c for c in nb4 if c["shear"] == 0])
+    for v, (env, _) in M.VARIANTS.items():
+        assert env["HNUMO_EXPERIMENTS"] == "1" and env["HNUMO_PERSISTENT"] == "0" and env["HNUMO_BCL_BIG"] == "1"
+        assert M.variant_overrides(v) == ["HNUMO_STAGE_NB=" + env["HNUMO_STAGE_NB"], "HNUMO_BCL_BIG=1",
+                                          "HNUMO_PERSISTENT=0"]
+    assert M.variant_kernels("large", 4) == dict(stage_arena=5, bcl_big=True)
+    assert M.variant_kernels("large-nb4", 4) == dict(stage_arena=4, bcl_big=True)
+    assert all(M.variant_kernels("large", N) == dict(stage_arena=0, bcl_big=True) for N in (2, 3, 5, 7))
+
+
 @pytest.mark.parametrize("name", [c["name"] for c in M.CELLS])
 def test_cell_sizes_and_time_steps(name, case_factory):
     from hnumo.case import CONFIGS
