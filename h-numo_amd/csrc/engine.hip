@@ -38,6 +38,7 @@
 #include "kernels_vort.hip"
 #include "kernels_sample.hip"
 #include "kernels_float.hip"
+#include "kernels_wind.hip"
 
 using namespace hnumo;
 
@@ -268,6 +269,15 @@ struct hnumo_engine {
   // the migrating sets' tables of a processor-face rank (float_xface; fl_xface_err: why not)
   std::vector<int32_t> fl_xface, fl_arrive;
   std::string fl_xface_err;
+  // time-dependent wind stress (hnumo_wind_begin .. hnumo_wind_end; kernels_wind.hip): the M patterns
+  // and the create-time tau_wind on the device; the schedule's coefficient table [nrows][M], the steps
+  // taken under it and the row the four homes of the wind hold now (-1: none of the table's)
+  struct Wind {
+    bool on = false;
+    int M = 0, nrows = 0, first = 0, mode = 0, applied = -1;
+    int64_t k = 0;
+    double *pat = nullptr, *tau0 = nullptr, *table = nullptr;
+  } wind;
 };
 
 // the per-kernel breakdown's mark after a launch on the engine stream (no-op outside
@@ -1401,6 +1411,171 @@ static int setup_persistent(hnumo_engine *eng, const SetupPlan &pl, const Knobs 
 // ------------------------------------------------------------------ observers of the resident state
 #include "observers.hip"
 
+// ------------------------------------------------------------------ time-dependent wind stress
+// (kernels_wind.hip; plain launches on the engine stream, outside the captured step: the four homes
+// of the wind keep their addresses, so the step graph stays valid)
+static_assert(WIND_MAXM == HNUMO_WIND_MAXM, "kernels_wind.hip and the header disagree on the number of patterns");
+
+static void wind_free(hnumo_engine *eng) {
+  auto &w = eng->wind;
+  dfree(w.pat, w.tau0, w.table);
+  w = hnumo_engine::Wind{};
+}
+
+// the blend of the begun patterns (pat NULL) or of `pat`, with the coefficients `row` of the device
+// table or `c`, into tau_wind, qstat, qstatE and tau_wind_ave
+static int wind_blend(hnumo_engine *eng, const double *pat, int M, const double *row, const double *c, const char *who) {
+  WindArgs a{};
+  a.pat = (const double2 *)(pat ? pat : eng->wind.pat);
+  a.row = row;
+  for (int m = 0; m < M && c; m++) a.c[m] = c[m];
+  a.tau = (double2 *)eng->tau_wind;
+  a.ave = (double2 *)eng->tau_wind_ave;
+  a.qstat = eng->qstat;
+  a.qstatE = eng->qstatE;
+  a.npq = eng->npq;
+  a.N_btp = eng->p.N_btp;
+  if (!wind_launch(a, M, eng->nq, eng->stream))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no blend kernel for M = " + std::to_string(M) +
+                                            ", nq = " + std::to_string(eng->nq));
+  HIPCHK(hipGetLastError());
+  return HNUMO_OK;
+}
+
+// the row of the schedule that step k uses (nrows > 0)
+static int wind_row(const hnumo_engine::Wind &w) {
+  const int64_t r = (int64_t)w.first + w.k;
+  return (int)(w.mode == HNUMO_WIND_REPEAT ? r % w.nrows : std::min<int64_t>(r, w.nrows - 1));
+}
+
+// before a step's launches: the schedule's row of this step, unless the wind holds it already
+static int wind_before_step(hnumo_engine *eng) {
+  auto &w = eng->wind;
+  if (!w.on || w.nrows == 0) return HNUMO_OK;
+  const int r = wind_row(w);
+  if (r == w.applied) return HNUMO_OK;
+  HIPCHK(hipSetDevice(eng->device));
+  if (int rc = wind_blend(eng, nullptr, w.M, w.table + (size_t)r * w.M, nullptr, "wind schedule")) return rc;
+  w.applied = r;
+  return HNUMO_OK;
+}
+
+static void wind_after_step(hnumo_engine *eng) {
+  if (eng->wind.on && eng->wind.nrows > 0) eng->wind.k++;
+}
+
+// what every call after hnumo_wind_begin checks first
+static int wind_begun(hnumo_engine *eng, const char *who, int M, bool with_M) {
+  if (!eng->wind.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_wind_begin first");
+  if (with_M && M != eng->wind.M)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": M = " + std::to_string(M) + " but hnumo_wind_begin took M = " +
+                                            std::to_string(eng->wind.M));
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_wind_begin(hnumo_engine *eng, const double *patterns, int64_t n, int32_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (M < 1 || M > WIND_MAXM)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_wind_begin: M must be 1.." + std::to_string(WIND_MAXM) + ", got " + std::to_string(M));
+  if (!patterns) return fail(eng, HNUMO_ERR_INVALID, "hnumo_wind_begin: patterns is NULL");
+  const int64_t want = 2 * (int64_t)eng->npq * M;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_wind_begin: n must be 2*npoin_q*M = " + std::to_string(want) + ", got " + std::to_string(n));
+  if (!wind_nq_ok(eng->nq) || eng->npq != eng->nelem * eng->nq * eng->nq)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_wind_begin: unsupported nq = " + std::to_string(eng->nq));
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a blend in flight reads the old patterns)
+  auto &w = eng->wind;
+  const size_t n2 = 2 * (size_t)eng->npq;
+  // the create-time wind is kept from the first begin on: the current one may be a blend already
+  const bool first = !w.on;
+  double *tau0 = w.tau0;
+  w.tau0 = nullptr;
+  wind_free(eng);
+  w.tau0 = tau0;
+  bool ok = alloc_doubles(&w.pat, n2 * M) && (!first || alloc_doubles(&w.tau0, n2));
+  ok = ok && hipMemcpy(w.pat, patterns, n2 * M * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  // (on the engine stream: ordered before any later blend, which writes its source)
+  if (ok && first)
+    ok = hipMemcpyAsync(w.tau0, eng->tau_wind, n2 * sizeof(double), hipMemcpyDeviceToDevice, eng->stream) == hipSuccess &&
+         hipStreamSynchronize(eng->stream) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    // (not begun any more: the create-time wind goes back where an earlier begin's blends changed it)
+    const double one = 1.0;
+    if (!first && wind_blend(eng, w.tau0, 1, nullptr, &one, "hnumo_wind_begin") == HNUMO_OK)
+      (void)hipStreamSynchronize(eng->stream);
+    wind_free(eng);
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_wind_begin: device allocation or upload failed");
+  }
+  w.M = M;
+  w.on = true;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_wind_set(hnumo_engine *eng, const double *coef, int32_t M) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (M < 1 || M > WIND_MAXM)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_wind_set: M must be 1.." + std::to_string(WIND_MAXM) + ", got " + std::to_string(M));
+  if (int rc = wind_begun(eng, "hnumo_wind_set", M, true)) return rc;
+  if (!coef) return fail(eng, HNUMO_ERR_INVALID, "hnumo_wind_set: coef is NULL");
+  HIPCHK(hipSetDevice(eng->device));
+  if (int rc = wind_blend(eng, nullptr, M, nullptr, coef, "hnumo_wind_set")) return rc;
+  eng->wind.applied = -1;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_wind_schedule(hnumo_engine *eng, const double *coef, int32_t M, int32_t nrows, int32_t first, int32_t mode) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_wind_schedule";
+  if (M < 1 || M > WIND_MAXM)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": M must be 1.." + std::to_string(WIND_MAXM) + ", got " + std::to_string(M));
+  if (int rc = wind_begun(eng, who, M, true)) return rc;
+  if (nrows < 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": nrows must be >= 0, got " + std::to_string(nrows));
+  if (first < 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": first must be >= 0, got " + std::to_string(first));
+  if (mode != HNUMO_WIND_HOLD && mode != HNUMO_WIND_REPEAT)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": mode must be HNUMO_WIND_HOLD or HNUMO_WIND_REPEAT, got " + std::to_string(mode));
+  if (nrows > 0 && !coef) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": coef is NULL");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a blend in flight reads the old table)
+  auto &w = eng->wind;
+  dfree(w.table);
+  w.nrows = 0, w.first = 0, w.mode = 0, w.k = 0, w.applied = -1;
+  if (nrows == 0) return HNUMO_OK;
+  const size_t nt = (size_t)M * nrows;
+  if (!alloc_doubles(&w.table, nt) || hipMemcpy(w.table, coef, nt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    dfree(w.table);
+    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
+  }
+  w.nrows = nrows, w.first = first, w.mode = mode;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_wind_get(hnumo_engine *eng, double *tau, int64_t n, int32_t *next_row) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (int rc = wind_begun(eng, "hnumo_wind_get", 0, false)) return rc;
+  if (!tau || !next_row) return fail(eng, HNUMO_ERR_INVALID, std::string("hnumo_wind_get: ") + (tau ? "next_row" : "tau") + " is NULL");
+  const int64_t want = 2 * (int64_t)eng->npq;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_wind_get: n must be 2*npoin_q = " + std::to_string(want) + ", got " + std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  *next_row = eng->wind.nrows > 0 ? wind_row(eng->wind) : -1;
+  return download(eng, tau, eng->tau_wind, (size_t)want * sizeof(double));
+}
+
+extern "C" int hnumo_wind_end(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (int rc = wind_begun(eng, "hnumo_wind_end", 0, false)) return rc;
+  HIPCHK(hipSetDevice(eng->device));
+  // 1.0 * tau0 is tau0 in every bit, and its average is formed as at create
+  const double one = 1.0;
+  if (int rc = wind_blend(eng, eng->wind.tau0, 1, nullptr, &one, "hnumo_wind_end")) return rc;
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  wind_free(eng);
+  return HNUMO_OK;
+}
+
 // ------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -1434,6 +1609,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   vort_free(eng);
   for (int id = 0; id < SP_MAXSETS; id++) sample_free(eng, id);
   for (int id = 0; id < FL_MAXSETS; id++) floats_free(eng, id);
+  wind_free(eng);
   if (eng->stream && eng->own_stream) (void)hipStreamDestroy(eng->stream);
   if (LocalGroup *g = eng->group) {
     // the destroyed engine cannot take part in exchanges any more; the last one out frees
@@ -1670,9 +1846,12 @@ int hnumo_ti_rk_bcl(hnumo_engine *eng, double *q_df, double *qb_df, double *qpri
     if (rc) return rc;
     eng->uploaded = true;
   }
-  int rc = run_steps(eng, 1);
+  int rc = wind_before_step(eng);
+  if (rc) return rc;
+  rc = run_steps(eng, 1);
   if (rc) return rc;
   if (!eng->resident && (rc = download_state(eng, q_df, qb_df, qprime_df))) return rc;
+  wind_after_step(eng);
   return observers_after_step(eng);
 }
 
@@ -2283,6 +2462,7 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
         rc[i] = upload_state(eng, q_df[i], qb_df[i], qprime_df[i]);
         eng->uploaded = true;
       }
+      if (!rc[i]) rc[i] = wind_before_step(eng);  // (each engine's own schedule)
       int r = rc[i] ? rc[i] : run_steps(eng, 1);
       if (!rc[i]) rc[i] = r;
       if (!rc[i] && !eng->resident) rc[i] = download_state(eng, q_df[i], qb_df[i], qprime_df[i]);
@@ -2292,6 +2472,7 @@ int hnumo_group_ti_rk_bcl(hnumo_engine **engines, int n, double **q_df, double *
   for (auto &t : th) t.join();
   for (int i = 0; i < n; i++)
     if (rc[i]) return rc[i];
+  for (int i = 0; i < n; i++) wind_after_step(engines[i]);
   // (the step of every engine succeeded: every engine's observers run, each on its engine's stream,
   // whatever another one returns; the first non-zero code is returned.  The migrating float sets come
   // last: their advance needs every engine, observers_after_step leaves them out)

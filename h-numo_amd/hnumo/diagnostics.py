@@ -282,7 +282,7 @@ def restart_state(case, path):
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
               time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1, floats=None,
-              vorticity=None, vort_every=1):
+              vorticity=None, vort_every=1, wind=None):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
@@ -310,7 +310,13 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     vort_every-th step of this loop (after flow_stats' sample, before the floats) the host object gets
     add(q) on the host arrays, which a resident stepper syncs for it first.  A device object was begun
     with its own `every`: the engine has taken its series sample already (no sync) and the loop leaves
-    it alone.  None: nothing changes."""
+    it alone.  None: nothing changes.
+
+    wind: a hnumo.wind.DeviceWind or HostWind; before every step of this loop it gets before_step(stepper, n)
+    with n the number of steps of the run taken so far (a restarted loop starts at restart_file_number
+    snapshots' worth of steps, so the schedule resumes where the run stopped).  The device object installs
+    its schedule on the engine at the first call and does nothing afterwards; the host object hands the
+    blended wind to a stepper that has set_tau_wind.  None: nothing changes."""
     if vorticity is not None and int(vort_every) < 1:
         raise ValueError("vort_every must be >= 1")
     float_sets = [] if floats is None else list(floats) if isinstance(floats, (list, tuple)) else [floats]
@@ -367,9 +373,12 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
         stepper.set_resident(True)
     stepped = False
     nstep = 0
+    step0 = 0 if time_initial == 0 else restart_file_number * irestart
     while time < time_final:
         itime += 1
         time = time + dt
+        if wind is not None:
+            wind.before_step(stepper, step0 + nstep)
         stepper.ti_rk_bcl(q, qb, qp)
         stepped = True
         nstep += 1

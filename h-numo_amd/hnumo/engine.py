@@ -107,6 +107,11 @@ def lib():
         L.hnumo_floats_settle.argtypes = [vp, i32]
         L.hnumo_group_floats_migrate.argtypes = [C.POINTER(vp), C.c_int, i32, i32, C.c_double]
         L.hnumo_group_floats_advance.argtypes = [C.POINTER(vp), C.c_int, i32, C.c_double]
+        L.hnumo_wind_begin.argtypes = [vp, dp, i64, i32]
+        L.hnumo_wind_set.argtypes = [vp, dp, i32]
+        L.hnumo_wind_schedule.argtypes = [vp, dp, i32, i32, i32, i32]
+        L.hnumo_wind_get.argtypes = [vp, dp, i64, ip]
+        L.hnumo_wind_end.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -584,6 +589,43 @@ class Engine:
     def floats_settle(self, fid: int):
         """Takes the record that an advance of a migrating set deferred."""
         self._check(lib().hnumo_floats_settle(self.h, int(fid)))
+
+    # ---- time-dependent wind stress (hnumo_wind_*; mirror and schedules: hnumo/wind.py)
+    def wind_begin(self, patterns):
+        """patterns (2, npoin_q, M), 1 <= M <= 4, over every local element.  The wind is unchanged until
+        wind_set or a scheduled step; again: replaces the patterns and clears the schedule."""
+        p = np.asfortranarray(patterns, dtype=np.float64)
+        if p.ndim == 2:
+            p = np.asfortranarray(p[:, :, None])
+        if p.ndim != 3 or p.shape[:2] != (2, self.dims["npoin_q"]):
+            raise ValueError(f"patterns: shape {p.shape}, expected (2, {self.dims['npoin_q']}, M)")
+        self._check(lib().hnumo_wind_begin(self.h, p.ctypes.data_as(C.POINTER(C.c_double)), p.size, p.shape[2]))
+
+    def wind_set(self, coef):
+        """tau_wind = coef[0]*T_0 + coef[1]*T_1 + ... now, for every later step (hnumo.wind.blend)."""
+        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        self._check(lib().hnumo_wind_set(self.h, c.ctypes.data_as(C.POINTER(C.c_double)), c.size))
+
+    def wind_schedule(self, coef, first: int = 0, mode=0):
+        """coef (M, nrows), copied to the device once: the k-th successful step from now uses row first + k,
+        held at the last row (mode "hold") or taken modulo nrows ("repeat").  No rows: clears the schedule."""
+        from .wind import _mode
+        t = np.asfortranarray(coef, dtype=np.float64)
+        if t.ndim != 2:
+            raise ValueError(f"coef: shape {t.shape}, expected (M, nrows)")
+        self._check(lib().hnumo_wind_schedule(self.h, t.ctypes.data_as(C.POINTER(C.c_double)), t.shape[0], t.shape[1],
+                                              int(first), _mode(mode)))
+
+    def wind_get(self):
+        """(tau_wind (2, npoin_q) on the device now, the row the next step will use or -1)."""
+        tau = np.zeros((2, self.dims["npoin_q"]), order="F")
+        r = C.c_int32(-2)
+        self._check(lib().hnumo_wind_get(self.h, _dp(tau), tau.size, C.byref(r)))
+        return tau, r.value
+
+    def wind_end(self):
+        """The create-time wind again, bit for bit; frees the patterns and the schedule."""
+        self._check(lib().hnumo_wind_end(self.h))
 
     def bench_steps(self, nsteps: int):
         t = C.c_double()

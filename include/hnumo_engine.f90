@@ -92,10 +92,12 @@ module hnumo_engine_c
         hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy, &
         hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
         hnumo_floats_begin, hnumo_floats_record, hnumo_floats_series, hnumo_floats_destroy, &
-        hnumo_floats_migrate, hnumo_floats_release, hnumo_floats_outbox, hnumo_floats_deliver, hnumo_floats_settle
+        hnumo_floats_migrate, hnumo_floats_release, hnumo_floats_outbox, hnumo_floats_deliver, hnumo_floats_settle, &
+        hnumo_wind_begin, hnumo_wind_set, hnumo_wind_schedule, hnumo_wind_get, hnumo_wind_end
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
     integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1, &
         HNUMO_SAMPLE_VORT = 2   ! sample set sources
+    integer(c_int32_t), parameter, public :: HNUMO_WIND_MAXM = 4, HNUMO_WIND_HOLD = 0, HNUMO_WIND_REPEAT = 1
     integer(c_int32_t), parameter, public :: HNUMO_FLOAT_ACTIVE = 0, HNUMO_FLOAT_LEFT = 1, HNUMO_FLOAT_LOST = 2   ! float status
 
     interface
@@ -554,6 +556,49 @@ module hnumo_engine_c
             type(c_ptr), value :: eng
             integer(c_int32_t), value :: id
         end function hnumo_floats_settle
+
+        ! ---- time-dependent wind stress (hnumo_wind_*, include/hnumo_engine.h): the wind as a linear
+        ! combination of M <= HNUMO_WIND_MAXM patterns, formed on the device
+        ! patterns(2,npoin_q,M), n = size(patterns); the wind is unchanged until a set or a scheduled step
+        integer(c_int) function hnumo_wind_begin(eng, patterns, n, M) bind(C, name='hnumo_wind_begin')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: patterns(*)
+            integer(c_int64_t), value :: n
+            integer(c_int32_t), value :: M
+        end function hnumo_wind_begin
+
+        ! tau_wind = coef(1)*T_1 + ... + coef(M)*T_M now, for every later step
+        integer(c_int) function hnumo_wind_set(eng, coef, M) bind(C, name='hnumo_wind_set')
+            import :: c_int, c_int32_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: coef(*)
+            integer(c_int32_t), value :: M
+        end function hnumo_wind_set
+
+        ! coef(M,nrows) copied to the device once; the k-th successful step since this call uses row
+        ! first + k (0-based), held at the last row (HNUMO_WIND_HOLD) or taken modulo nrows (HNUMO_WIND_REPEAT)
+        integer(c_int) function hnumo_wind_schedule(eng, coef, M, nrows, first, mode) bind(C, name='hnumo_wind_schedule')
+            import :: c_int, c_int32_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: coef(*)
+            integer(c_int32_t), value :: M, nrows, first, mode
+        end function hnumo_wind_schedule
+
+        ! tau(2,npoin_q), n = size(tau): the current wind; next_row: the row the next step uses (-1: none)
+        integer(c_int) function hnumo_wind_get(eng, tau, n, next_row) bind(C, name='hnumo_wind_get')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: tau(*)
+            integer(c_int64_t), value :: n
+            integer(c_int32_t), intent(out) :: next_row
+        end function hnumo_wind_get
+
+        ! the create-time wind again, bit for bit
+        integer(c_int) function hnumo_wind_end(eng) bind(C, name='hnumo_wind_end')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_wind_end
     end interface
 
 contains

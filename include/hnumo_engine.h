@@ -539,6 +539,45 @@ int hnumo_floats_deliver(hnumo_engine *eng, int32_t id, int32_t src_rank, const 
                          int64_t n);
 int hnumo_floats_settle(hnumo_engine *eng, int32_t id);
 
+/* Time-dependent wind stress (additive in ABI v10; no reference counterpart: the reference sets
+ * tau_wind once, initial_conditions.F90:190, and reads it as plain data).  A few wind patterns are
+ * uploaded once and a linear combination of them is formed on the device, so a wind that is ramped
+ * up or follows a seasonal cycle needs neither a new engine nor a copy per step.  Arithmetic
+ * (normative; IEEE double, no FMA), per component and quad point, for patterns T_m(2,npoin_q),
+ * m = 0..M-1 with 1 <= M <= HNUMO_WIND_MAXM, over every local element (the ghost elements of a
+ * ghost-layer partition included), and coefficients c_0..c_{M-1}:
+ *     tau = c_0*T_0;  for m = 1..M-1: tau = tau + c_m*T_m        (left to right, product first)
+ *     s = 0.0;  N_btp times: s = s + tau;  tau_wind_ave = s / double(N_btp)
+ * An engine whose wind was set to tau is, bit for bit, an engine created with tau.
+ *   hnumo_wind_begin     patterns(2,npoin_q,M), n = 2*npoin_q*M; keeps a copy of the create-time wind.
+ *                        The wind is unchanged until a set or a scheduled step.  Again: replaces
+ *                        the patterns and clears the schedule.
+ *   hnumo_wind_set       blends now: for every later step, parity hook and hnumo_bench_steps.
+ *   hnumo_wind_schedule  coef(M,nrows) is copied to the device once.  With k the number of successful
+ *                        hnumo_ti_rk_bcl / hnumo_group_ti_rk_bcl calls since this call, step k uses row
+ *                        r = first + k, applied before the step's launches: HNUMO_WIND_HOLD keeps the
+ *                        last row beyond the table (and launches nothing more), HNUMO_WIND_REPEAT takes
+ *                        r mod nrows.  nrows = 0 clears the schedule.  A step that returns non-zero
+ *                        leaves k where it was; a step the engine redoes after a persistent launch
+ *                        gave up consumes one row.  The parity hooks, hnumo_bench_steps and
+ *                        hnumo_step_breakdown use the wind in place and never advance k.  In a local
+ *                        group every engine follows its own schedule.
+ *   hnumo_wind_get       the current tau_wind (n = 2*npoin_q) and the row the next step will use
+ *                        (-1: no schedule).
+ *   hnumo_wind_end       restores the create-time wind, bit for bit, and frees everything
+ *                        (hnumo_engine_destroy frees a begun wind too).
+ * Code 4, with the call and the value in the message: M outside 1..HNUMO_WIND_MAXM or different from
+ * begin's, a NULL pointer, a wrong n, set / schedule / get / end before begin, nrows < 0, first < 0,
+ * an unknown mode.                                                                         */
+#define HNUMO_WIND_MAXM 4
+#define HNUMO_WIND_HOLD 0
+#define HNUMO_WIND_REPEAT 1
+int hnumo_wind_begin(hnumo_engine *eng, const double *patterns, int64_t n, int32_t M);
+int hnumo_wind_set(hnumo_engine *eng, const double *coef, int32_t M);
+int hnumo_wind_schedule(hnumo_engine *eng, const double *coef, int32_t M, int32_t nrows, int32_t first, int32_t mode);
+int hnumo_wind_get(hnumo_engine *eng, double *tau, int64_t n, int32_t *next_row);
+int hnumo_wind_end(hnumo_engine *eng);
+
 /* Summation order of the barotropic stage (no reference counterpart: the reference has
  * one order).  HNUMO_SUM_REFERENCE (the default) evaluates the volume integral and the
  * nodal -> quad interpolation as the reference's dense psih/dpsidx sums in its order:
