@@ -256,6 +256,9 @@ struct hnumo_engine {
     int *d_i = nullptr;                    // elem | layer | status | fresh | perm, [M] each
     int every = 0;
     Series series;
+    // sensors (hnumo_floats_sensors): the mask, whose S rows follow the 5 of a record; hnumo_floats_sense's [S][M]
+    int sensors = 0;
+    double *d_sense = nullptr;
     // migration (hnumo_floats_migrate): the tol_e in use are those of coord_scale when it is > 0; xface | arrive |
     // iperm on the device; three boxes of M flight records (outbox 0, outbox 1, the inbox of hnumo_floats_deliver)
     // and the two outbox counters; the outbox the next advance or arrival writes; a record the advance deferred

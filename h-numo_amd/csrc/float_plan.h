@@ -635,6 +635,232 @@ inline void float_arrive_ngl(const FloatRank &rk, const FloatField &f, int nlaye
   }
 }
 
+// ------------------------------------------------------------------ sensors (include/hnumo_engine.h has the normative text)
+// A set's sensor mask adds S rows to a record: STATE (1) h, u, v, dp, elevation and VORT (2) zeta, delta, pv, ow of
+// the float's own layer, each the value a hnumo_sample_create_ref set reads at the float's cached (elem, xi, eta).
+// float_sense_kernel (kernels_float.hip) and float_sense_host below run the same text: the slot rule
+// (float_sense_slots is its sequential statement; the kernel forms it with a ballot), the forming of an element's
+// nodal fields into an arena of K element slots with an odd stride, and the double sum.  The forming statements
+// restate diag_layer_fields (kernels_diag.hip) and vort_node (kernels_vort.hip), which sample_kernel is compiled
+// from and which stay as they are.
+constexpr int FL_SENSE_STATE = 1, FL_SENSE_VORT = 2;   // HNUMO_FLOAT_SENSE_STATE, HNUMO_FLOAT_SENSE_VORT
+constexpr int FL_SENSE_ALL = FL_SENSE_STATE | FL_SENSE_VORT;
+constexpr int FL_SENSE_LDS_BYTES = 32768;              // the kernel's arena
+
+// rows per float, rows per element in the arena (every layer: the floats of an element lie in any), the arena's
+// element stride in doubles (odd: consecutive slots start on different LDS banks) and its element slots K
+constexpr int fl_sense_rows(int mask) { return (mask & FL_SENSE_STATE ? 5 : 0) + (mask & FL_SENSE_VORT ? 4 : 0); }
+constexpr int fl_sense_nval(int L, int mask) { return fl_sense_rows(mask) * L; }
+constexpr int fl_sense_estride(int ngl, int L, int mask) { return (fl_sense_nval(L, mask) * ngl * ngl) | 1; }
+constexpr int fl_sense_K(int ngl, int L, int mask) {
+  return mask ? FL_SENSE_LDS_BYTES / (8 * fl_sense_estride(ngl, L, mask)) : 0;
+}
+
+// what the sensors read beside the floats: the state, the statics of diag_layer_fields and of vort_node
+struct FloatSense {
+  const double *q;                  // q_df(3, npoin, L)
+  const double *zbot, *alpha;       // zbot_df(npoin), alpha_mlswe(L)
+  const double *ex, *ey, *nx, *ny;  // ksi_x, ksi_y, eta_x, eta_y (npoin)
+  const double *f;                  // coriolis_df(npoin) as hnumo_vort_begin took it, or NULL: 0
+  const double *dpsi;               // D(m,i) at [m*ngl + i]
+  double gravity;
+  size_t npoin;
+  double xgl[8];
+};
+
+// The slot rule for n consecutive floats of a set (one workgroup's; elem 1-based, <= 0: inactive): a float is a
+// head when it is active and it is the first, or the float before it is inactive or lies in another element; the
+// slot of an active float is the inclusive count of heads up to it, minus 1 (-1 for an inactive one); list[slot] =
+// the head's element, 0-based.  Returns the number of slots.  An element that turns up in two separate runs gets
+// two slots.
+inline int float_sense_slots(const int32_t *elem, int n, int32_t *slot, int32_t *list) {
+  int ns = 0;
+  for (int t = 0; t < n; t++) {
+    if (elem[t] <= 0) {
+      slot[t] = -1;
+      continue;
+    }
+    if (t == 0 || elem[t - 1] <= 0 || elem[t - 1] != elem[t]) list[ns++] = elem[t] - 1;
+    slot[t] = ns - 1;
+  }
+  return ns;
+}
+
+// STATE: the rows 5k..5k+4 = h, u, v, dp, elevation of node I into s[(5k + v) * P] (diag_layer_fields' statements)
+template <int NGL, int L>
+HNUMO_HD inline void float_sense_form_state(const FloatSense &g, const double (&ag)[L], size_t I, double *s) {
+  constexpr int P = NGL * NGL;
+  double f[L][5];
+#pragma unroll
+  for (int k = 0; k < L; k++) {
+    const double *p = g.q + 3 * (I + g.npoin * k);
+    const double dp = p[0];
+    f[k][0] = ag[k] * dp;
+    f[k][1] = p[1] / dp;
+    f[k][2] = p[2] / dp;
+    f[k][3] = dp;
+  }
+  double elev = g.zbot[I];
+#pragma unroll
+  for (int k = L - 1; k >= 0; k--) {
+    elev = elev + f[k][0];
+    f[k][4] = elev;
+  }
+#pragma unroll
+  for (int k = 0; k < L; k++)
+#pragma unroll
+    for (int v = 0; v < 5; v++) s[(5 * k + v) * P] = f[k][v];
+}
+
+// VORT, the three steps of sample_kernel's VORT source for node I = (i, j) of an element whose rows start at se,
+// s = se + j*NGL + i.  1: u, v of every layer into rows 4k+2, 4k+3, h kept.  (All nodes of the element, then) 2: zeta,
+// delta into rows 4k, 4k+1, pv and ow kept (vort_node's statements).  (All nodes, then) 3: pv, ow into rows 4k+2, 4k+3.
+template <int NGL, int L>
+HNUMO_HD inline void float_sense_vort_uv(const FloatSense &g, const double (&ag)[L], size_t I, double *s, double (&h)[L]) {
+  constexpr int P = NGL * NGL;
+#pragma unroll
+  for (int k = 0; k < L; k++) {
+    const double *p = g.q + 3 * (I + g.npoin * k);
+    const double dp = p[0];
+    h[k] = ag[k] * dp;
+    s[(4 * k + 2) * P] = p[1] / dp;
+    s[(4 * k + 3) * P] = p[2] / dp;
+  }
+}
+
+template <int NGL, int L>
+HNUMO_HD inline void float_sense_vort_node(const FloatSense &g, size_t I, int i, int j, const double *se, double *s,
+                                           const double (&h)[L], double (&pvow)[L][2]) {
+  constexpr int P = NGL * NGL;
+  double Di[NGL], Dj[NGL];
+#pragma unroll
+  for (int m = 0; m < NGL; m++) {
+    Di[m] = g.dpsi[m * NGL + i];
+    Dj[m] = g.dpsi[m * NGL + j];
+  }
+  const double ex = g.ex[I], ey = g.ey[I], nx = g.nx[I], ny = g.ny[I];
+  const double f = g.f ? g.f[I] : 0.0;
+#pragma unroll
+  for (int k = 0; k < L; k++) {
+    const double *su = se + (4 * k + 2) * P, *sv = se + (4 * k + 3) * P;
+    const double *ur = su + j * NGL, *vr = sv + j * NGL, *uc = su + i, *vc = sv + i;
+    double u_xi = Di[0] * ur[0], u_eta = Dj[0] * uc[0], v_xi = Di[0] * vr[0], v_eta = Dj[0] * vc[0];
+#pragma unroll
+    for (int m = 1; m < NGL; m++) {
+      u_xi = u_xi + Di[m] * ur[m];
+      u_eta = u_eta + Dj[m] * uc[m * NGL];
+      v_xi = v_xi + Di[m] * vr[m];
+      v_eta = v_eta + Dj[m] * vc[m * NGL];
+    }
+    const double u_x = u_xi * ex + u_eta * nx, u_y = u_xi * ey + u_eta * ny;
+    const double v_x = v_xi * ex + v_eta * nx, v_y = v_xi * ey + v_eta * ny;
+    const double zeta = v_x - u_y;
+    const double sn = u_x - v_y, ss = v_x + u_y;
+    s[(4 * k) * P] = zeta;
+    s[(4 * k + 1) * P] = u_x + v_y;
+    pvow[k][0] = (zeta + f) / h[k];
+    pvow[k][1] = (sn * sn + ss * ss) - zeta * zeta;
+  }
+}
+
+template <int NGL, int L>
+HNUMO_HD inline void float_sense_vort_store(double *s, const double (&pvow)[L][2]) {
+  constexpr int P = NGL * NGL;
+#pragma unroll
+  for (int k = 0; k < L; k++) {
+    s[(4 * k + 2) * P] = pvow[k][0];
+    s[(4 * k + 3) * P] = pvow[k][1];
+  }
+}
+
+// a float's 2 NGL weights (float_vel's statement) and one row of its value from the tile f[j*NGL + i]
+template <int NGL>
+HNUMO_HD inline void float_sense_weights(const double *xgl, double xi, double eta, double (&lx)[NGL], double (&ly)[NGL]) {
+#pragma unroll
+  for (int i = 0; i < NGL; i++) {
+    double wx = 1.0, wy = 1.0;
+#pragma unroll
+    for (int m = 0; m < NGL; m++)
+      if (m != i) {
+        wx = wx * ((xi - xgl[m]) / (xgl[i] - xgl[m]));
+        wy = wy * ((eta - xgl[m]) / (xgl[i] - xgl[m]));
+      }
+    lx[i] = wx;
+    ly[i] = wy;
+  }
+}
+
+template <int NGL>
+HNUMO_HD inline double float_sense_value(const double *f, const double (&lx)[NGL], const double (&ly)[NGL]) {
+  double val = 0.0;
+#pragma unroll
+  for (int j = 0; j < NGL; j++) {
+    double r = lx[0] * f[j * NGL];
+#pragma unroll
+    for (int i = 1; i < NGL; i++) r = r + lx[i] * f[j * NGL + i];
+    val = j == 0 ? ly[0] * r : val + ly[j] * r;
+  }
+  return val;
+}
+
+// the S rows of a float of layer k (0-based) whose element's rows start at se, into o[row * stride]
+template <int NGL, int L, int MASK>
+HNUMO_HD inline void float_sense_rows_of(const double *se, int k, const double (&lx)[NGL], const double (&ly)[NGL], double *o,
+                                         size_t stride) {
+  constexpr int P = NGL * NGL, VO = MASK & FL_SENSE_STATE ? 5 * L : 0;
+  int row = 0;
+  if constexpr ((MASK & FL_SENSE_STATE) != 0) {
+#pragma unroll
+    for (int v = 0; v < 5; v++) o[(size_t)(row++) * stride] = float_sense_value<NGL>(se + (5 * k + v) * P, lx, ly);
+  }
+  if constexpr ((MASK & FL_SENSE_VORT) != 0) {
+#pragma unroll
+    for (int v = 0; v < 4; v++) o[(size_t)(row++) * stride] = float_sense_value<NGL>(se + (VO + 4 * k + v) * P, lx, ly);
+  }
+}
+
+// The host statement of float_sense_kernel<NGL, L, MASK>: out [S][M] planar, in input order; K: the element slots
+// of a pass (the kernel's fl_sense_K; any K >= 1 gives the same bits).
+template <int NGL, int L, int MASK>
+inline void float_sense_host_t(const FloatSense &g, const FloatPlan &p, int K, double *out) {
+  constexpr int P = NGL * NGL, S = fl_sense_rows(MASK), ES = fl_sense_estride(NGL, L, MASK), VO = MASK & FL_SENSE_STATE ? 5 * L : 0;
+  const size_t M = (size_t)p.M;
+  std::vector<double> arena((size_t)K * ES);
+  double ag[L];
+  for (int k = 0; k < L; k++) ag[k] = g.alpha[k] / g.gravity;
+  for (size_t b0 = 0; b0 < M; b0 += FL_BLOCK) {
+    const int n = (int)std::min<size_t>(FL_BLOCK, M - b0);
+    int32_t slot[FL_BLOCK], list[FL_BLOCK];
+    const int nslots = float_sense_slots(p.elem.data() + b0, n, slot, list);
+    for (int p0 = 0; p0 < nslots; p0 += K) {
+      const int nel = std::min(K, nslots - p0);
+      for (int le = 0; le < nel; le++) {
+        double *se = arena.data() + (size_t)le * ES;
+        const size_t I0 = (size_t)list[p0 + le] * P;
+        if constexpr ((MASK & FL_SENSE_STATE) != 0)
+          for (int ln = 0; ln < P; ln++) float_sense_form_state<NGL, L>(g, ag, I0 + ln, se + ln);
+        if constexpr ((MASK & FL_SENSE_VORT) != 0) {
+          double h[P][L], pvow[P][L][2];
+          for (int ln = 0; ln < P; ln++) float_sense_vort_uv<NGL, L>(g, ag, I0 + ln, se + VO * P + ln, h[ln]);
+          for (int ln = 0; ln < P; ln++)
+            float_sense_vort_node<NGL, L>(g, I0 + ln, ln % NGL, ln / NGL, se + VO * P, se + VO * P + ln, h[ln], pvow[ln]);
+          for (int ln = 0; ln < P; ln++) float_sense_vort_store<NGL, L>(se + VO * P + ln, pvow[ln]);
+        }
+      }
+      for (int t = 0; t < n; t++) {
+        if (slot[t] < p0 || slot[t] >= p0 + nel) continue;
+        const size_t s = b0 + t;
+        double lx[NGL], ly[NGL];
+        float_sense_weights<NGL>(g.xgl, p.xi[s], p.eta[s], lx, ly);
+        float_sense_rows_of<NGL, L, MASK>(arena.data() + (size_t)(slot[t] - p0) * ES, p.layer[s] - 1, lx, ly, out + p.perm[s], M);
+      }
+    }
+    for (int t = 0; t < n; t++)
+      if (slot[t] < 0)
+        for (int v = 0; v < S; v++) out[(size_t)v * M + p.perm[b0 + t]] = 0.0;
+  }
+}
+
 template <class F>
 inline void float_with_ngl(int ngl, F &&fn) {
   switch (ngl) {
@@ -644,6 +870,33 @@ inline void float_with_ngl(int ngl, F &&fn) {
     case 6: fn(std::integral_constant<int, 6>{}); break;
     default: fn(std::integral_constant<int, 8>{}); break;
   }
+}
+
+// fn(integral_constant L, integral_constant MASK) for L in 1..3 and a mask in 1..3
+template <class F>
+inline void float_with_L_mask(int L, int mask, F &&fn) {
+  auto with_mask = [&](auto l) {
+    switch (mask) {
+      case FL_SENSE_STATE: fn(l, std::integral_constant<int, FL_SENSE_STATE>{}); break;
+      case FL_SENSE_VORT: fn(l, std::integral_constant<int, FL_SENSE_VORT>{}); break;
+      default: fn(l, std::integral_constant<int, FL_SENSE_ALL>{}); break;
+    }
+  };
+  switch (L) {
+    case 1: with_mask(std::integral_constant<int, 1>{}); break;
+    case 2: with_mask(std::integral_constant<int, 2>{}); break;
+    default: with_mask(std::integral_constant<int, 3>{}); break;
+  }
+}
+
+// the sensors of the whole set on the host, in passes of K element slots (K <= 0: the kernel's)
+inline void float_sense_host(int ngl, int L, int mask, const FloatSense &g, const FloatPlan &p, int K, double *out) {
+  float_with_ngl(ngl, [&](auto n) {
+    float_with_L_mask(L, mask, [&](auto l, auto m) {
+      constexpr int NGL = decltype(n)::value, LL = decltype(l)::value, MASK = decltype(m)::value;
+      float_sense_host_t<NGL, LL, MASK>(g, p, K > 0 ? K : fl_sense_K(NGL, LL, MASK), out);
+    });
+  });
 }
 
 }  // namespace hnumo

@@ -22,7 +22,8 @@
 //          r_j, the r_j go round by shuffles and every lane adds Ly[j] * r_j in order of j: each sum
 //          is still one lane's, so the bits are those of G = 1.  Lane 0 of the group stores.
 // float_record_kernel appends a record (x, y, u, v, elem) to the planar series at the floats' input
-// positions.
+// positions; float_sense_kernel<NGL, L, MASK> (at the end of this file, the one kernel here with LDS)
+// appends the S rows of the set's sensors behind it.
 //
 // Migrating sets (processor-face ranks): float_advance_kernel<NGL, 1, true> is the same advance with
 // float_plan.h's MIG flag: a lane whose float reaches a processor face appends its flight record to the
@@ -225,6 +226,103 @@ __global__ void __launch_bounds__(FL_BLOCK) float_record_kernel(FloatArgs a) {
   o[2 * a.M] = a.wx[s];
   o[3 * a.M] = a.wy[s];
   o[4 * a.M] = (double)a.elem[s];
+}
+
+// float_sense_kernel<NGL, L, MASK>: the sensor rows of a record (float_plan.h has the statements, which its host
+// evaluation float_sense_host_t runs too).  One workgroup per FL_BLOCK consecutive slots of the set's sorted order.
+//   Slots: a lane is a head when its float is active (elem > 0) and it is lane 0 or the float before it is inactive
+//   or in another element; a wave counts its heads with a ballot, the lane's inclusive count is the popcount of the
+//   ballot up to its own bit, the four waves' totals go through LDS; heads publish their element in s_list.
+//   Passes of K slots (the trip count ceil(nslots / K) is the workgroup's, so every lane reaches every barrier):
+//   the nodal fields of the pass's elements go into the arena of K * ES doubles (ES odd) -- STATE one node per lane
+//   in a strided loop, VORT in passes of 256/P whole elements with sample_kernel's u, v -> barrier -> derivative
+//   sums -> barrier -> pv, ow sequence; consecutive lanes read consecutive nodes of q.  One barrier.  A lane whose
+//   slot lies in the pass forms its 2 NGL weights in registers, evaluates its S rows of its own layer (lanes of one
+//   element read the same words: broadcasts) and writes out[row][perm[s]].  One barrier before the next pass.
+//   Inactive floats write S zeros.
+// No atomics, nothing between workgroups; every loop over registers has compile-time bounds; a value is one lane's
+// sum, so the grouping (and an element that takes two slots) cannot change a bit.
+struct FloatSenseArgs {
+  FloatSense g;
+  const double *xi, *eta;
+  const int *elem, *layer, *perm;
+  double *out;                             // [S][M]
+  size_t M;
+};
+
+template <int NGL, int L, int MASK>
+__global__ void __launch_bounds__(FL_BLOCK) float_sense_kernel(FloatSenseArgs a) {
+  constexpr int P = NGL * NGL, S = fl_sense_rows(MASK), ES = fl_sense_estride(NGL, L, MASK), K = fl_sense_K(NGL, L, MASK);
+  constexpr int VO = MASK & FL_SENSE_STATE ? 5 * L : 0, NW = FL_BLOCK / 64;
+  static_assert(K >= 1, "the arena holds no element");
+  static_assert(FL_BLOCK % 64 == 0, "whole waves");
+  __shared__ double s_f[K * ES];
+  __shared__ int s_list[FL_BLOCK];
+  __shared__ int s_heads[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t s = (size_t)blockIdx.x * FL_BLOCK + tid;
+  const bool in = s < a.M;
+  const int e = in ? a.elem[s] : 0;
+  const bool active = e > 0;
+  const int before = (in && tid > 0) ? a.elem[s - 1] : 0;
+  const bool head = active && (tid == 0 || before <= 0 || before != e);
+  const unsigned long long heads = __ballot(head);
+  if (lane == 0) s_heads[wave] = __popcll(heads);
+  __syncthreads();
+  int base = 0, nslots = 0;
+#pragma unroll
+  for (int w = 0; w < NW; w++) {
+    const int c = s_heads[w];
+    base += w < wave ? c : 0;
+    nslots += c;
+  }
+  const int slot = active ? base + __popcll(heads & (~0ull >> (63 - lane))) - 1 : -1;
+  if (head) s_list[slot] = e - 1;
+  __syncthreads();
+
+  double ag[L];
+#pragma unroll
+  for (int k = 0; k < L; k++) ag[k] = a.g.alpha[k] / a.g.gravity;
+  for (int p0 = 0; p0 < nslots; p0 += K) {       // (nslots is the workgroup's: every lane makes every pass)
+    const int nel = nslots - p0 < K ? nslots - p0 : K;
+    if constexpr ((MASK & FL_SENSE_STATE) != 0) {
+      for (int t = tid; t < nel * P; t += FL_BLOCK) {
+        const int le = t / P, ln = t - le * P;
+        float_sense_form_state<NGL, L>(a.g, ag, (size_t)s_list[p0 + le] * P + ln, s_f + le * ES + ln);
+      }
+    }
+    if constexpr ((MASK & FL_SENSE_VORT) != 0) {
+      constexpr int EPI = FL_BLOCK / P;            // whole elements per pass
+      const int le0 = tid / P, ln = tid - le0 * P, j = ln / NGL, i = ln - j * NGL;
+      for (int b = 0; b < nel; b += EPI) {
+        const int le = b + le0;
+        const bool act = tid < EPI * P && le < nel;
+        double *se = s_f + (act ? le : 0) * ES + VO * P;
+        size_t I = 0;
+        double h[L], pvow[L][2];
+        if (act) {
+          I = (size_t)s_list[p0 + le] * P + ln;
+          float_sense_vort_uv<NGL, L>(a.g, ag, I, se + ln, h);
+        }
+        __syncthreads();
+        if (act) float_sense_vort_node<NGL, L>(a.g, I, i, j, se, se + ln, h, pvow);
+        __syncthreads();
+        if (act) float_sense_vort_store<NGL, L>(se + ln, pvow);
+      }
+    }
+    __syncthreads();
+    if (active && slot >= p0 && slot < p0 + nel) {
+      double lx[NGL], ly[NGL];
+      float_sense_weights<NGL>(a.g.xgl, a.xi[s], a.eta[s], lx, ly);
+      float_sense_rows_of<NGL, L, MASK>(s_f + (slot - p0) * ES, a.layer[s] - 1, lx, ly, a.out + a.perm[s], a.M);
+    }
+    __syncthreads();
+  }
+  if (in && !active) {
+    double *o = a.out + a.perm[s];
+#pragma unroll
+    for (int v = 0; v < S; v++) o[(size_t)v * a.M] = 0.0;
+  }
 }
 
 }  // namespace hnumo

@@ -650,7 +650,7 @@ extern "C" int hnumo_sample_destroy(hnumo_engine *eng, int32_t id) {
 // ------------------------------------------------------------------ float sets
 // eng->floats[]: the host geometry (float_plan.h; hnumo_floats_set locates in it), the permutation
 // back to input order, the element tables and the SoA floats on the device, the series
-// [capacity][5][M].  The floats' own rules sit on top of the Series: `every` (0 or 1) is whether the
+// [capacity][5 + S][M] (S: the rows of the set's sensor mask).  The floats' own rules sit on top of the Series: `every` (0 or 1) is whether the
 // engine advances the set after a step; the series counts advances, not steps, and its every is the
 // caller's record_every
 using FloatSet = hnumo_engine::FloatSet;
@@ -658,7 +658,7 @@ using FloatSet = hnumo_engine::FloatSet;
 static void floats_free(hnumo_engine *eng, int id) {
   auto &s = eng->floats[id];
   dfree(s.d_geo, s.d_nbr, s.d_f, s.d_i, s.d_mig, s.d_boxi);
-  dfree(s.d_boxd);
+  dfree(s.d_boxd, s.d_sense);
   series_free(s.series);
   s = FloatSet{};
 }
@@ -761,13 +761,60 @@ static FloatArgs floats_args(hnumo_engine *eng, const FloatSet &s) {
   return a;
 }
 
+// ---- sensors: S rows behind the 5 of a record (float_sense_kernel)
+static int floats_nrows(const FloatSet &s) { return FL_NREC + fl_sense_rows(s.sensors); }
+
+// why the set's sensors cannot be read now, or 0
+static int floats_sense_refused(hnumo_engine *eng, const FloatSet &s, const char *who) {
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set's sensors read the state and there is none on the device yet (run a step first)");
+  if ((s.sensors & FL_SENSE_VORT) && !eng->vort.on)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set's sensors hold HNUMO_FLOAT_SENSE_VORT, which needs f: hnumo_vort_end "
+                                            "has been called (call hnumo_vort_begin again)");
+  return 0;
+}
+
+// the S sensor rows of the set into dst [S][M] on the device (input order), ordered after what is on the engine stream
+static int floats_sense_launch(hnumo_engine *eng, const FloatSet &s, double *dst) {
+  const FloatArgs f = floats_args(eng, s);
+  FloatSenseArgs a{};
+  a.g.q = eng->q;
+  a.g.zbot = eng->nstat + (size_t)NS_ZB * eng->npoin;
+  a.g.alpha = eng->alpha;
+  a.g.ex = eng->nstat + (size_t)NS_EX * eng->npoin;
+  a.g.ey = eng->nstat + (size_t)NS_EY * eng->npoin;
+  a.g.nx = eng->nstat + (size_t)NS_NX * eng->npoin;
+  a.g.ny = eng->nstat + (size_t)NS_NY * eng->npoin;
+  a.g.f = eng->vort.f;
+  a.g.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
+  a.g.gravity = eng->p.gravity;
+  a.g.npoin = (size_t)eng->npoin;
+  for (int i = 0; i < s.geom.ngl; i++) a.g.xgl[i] = s.geom.xgl[i];
+  a.xi = f.xi, a.eta = f.eta, a.elem = f.elem, a.layer = f.layer, a.perm = f.perm;
+  a.out = dst;
+  a.M = f.M;
+  const dim3 grid((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK));
+  with_ngl(eng->ngl, [&](auto ngl) {
+    float_with_L_mask(eng->L, s.sensors, [&](auto l, auto m) {
+      constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value, MASK = decltype(m)::value;
+      hipLaunchKernelGGL((float_sense_kernel<NGL, L, MASK>), grid, dim3(FL_BLOCK), 0, eng->stream, a);
+    });
+  });
+  HIPCHK(hipGetLastError());
+  return HNUMO_OK;
+}
+
 // one record of the set into the series, ordered after what is on the engine stream
 static int floats_record(hnumo_engine *eng, FloatSet &s, int id, const char *who) {
   if (int rc = series_full(eng, s.series, who, "the series of float set " + std::to_string(id), "records", "recorded")) return rc;
+  if (s.sensors)
+    if (int rc = floats_sense_refused(eng, s, who)) return rc;
   FloatArgs a = floats_args(eng, s);
   a.rec = series_slot(s.series);
   hipLaunchKernelGGL(float_record_kernel, dim3((unsigned)((a.M + FL_BLOCK - 1) / FL_BLOCK)), dim3(FL_BLOCK), 0, eng->stream, a);
   HIPCHK(hipGetLastError());
+  if (s.sensors)
+    if (int rc = floats_sense_launch(eng, s, a.rec + FL_NREC * a.M)) return rc;
   s.series.count++;
   return HNUMO_OK;
 }
@@ -836,7 +883,7 @@ extern "C" int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, 
   s->every = 0;
   s->settle_due = false;
   // (record_every holds with capacity 0 too: the record that falls due is then refused as into a full series)
-  if (series_begin(eng, s->series, FL_NREC * (size_t)s->M, record_every, capacity, false) != hipSuccess)
+  if (series_begin(eng, s->series, (size_t)floats_nrows(*s) * (size_t)s->M, record_every, capacity, false) != hipSuccess)
     return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_begin: device allocation failed");
   s->every = every;
   return HNUMO_OK;
@@ -898,7 +945,71 @@ extern "C" int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, i
   if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_series");
   if (!s) return HNUMO_ERR_INVALID;
-  return series_read(eng, s->series, FL_NREC, (size_t)s->M, out, n, count, clear, "hnumo_floats_series", "5*M");
+  return series_read(eng, s->series, floats_nrows(*s), (size_t)s->M, out, n, count, clear, "hnumo_floats_series",
+                     s->sensors ? "(5+S)*M" : "5*M");
+}
+
+extern "C" int hnumo_floats_sensors(hnumo_engine *eng, int32_t id, int32_t mask) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_floats_sensors";
+  auto *s = floats_set(eng, id, who);
+  if (!s) return HNUMO_ERR_INVALID;
+  if (mask < 0 || (mask & ~FL_SENSE_ALL))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": mask must be a sum of HNUMO_FLOAT_SENSE_STATE (1) and HNUMO_FLOAT_SENSE_VORT (2), got " +
+                                            std::to_string(mask));
+  if ((mask & FL_SENSE_VORT) && !eng->vort.on)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": HNUMO_FLOAT_SENSE_VORT needs f: call hnumo_vort_begin first");
+  if (s->series.cap > 0 && fl_sense_rows(mask) != fl_sense_rows(s->sensors))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the series of float set " + std::to_string(id) + " holds records of " +
+                                            std::to_string(floats_nrows(*s)) + " rows, the mask asks for " +
+                                            std::to_string(FL_NREC + fl_sense_rows(mask)) +
+                                            ": call hnumo_floats_begin with capacity 0 first, then hnumo_floats_sensors, then hnumo_floats_begin");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a record in flight runs the old mask's kernel)
+  s->sensors = mask;
+  if (s->series.cap == 0) s->series.width = (size_t)floats_nrows(*s) * (size_t)s->M;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_sense_info(hnumo_engine *eng, int32_t id, int32_t *nrows, int32_t *K) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = floats_set(eng, id, "hnumo_floats_sense_info");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (nrows) *nrows = fl_sense_rows(s->sensors);
+  if (K) {
+    *K = 0;
+    if (s->sensors)
+      with_ngl(eng->ngl, [&](auto ngl) {
+        float_with_L_mask(eng->L, s->sensors, [&](auto l, auto m) {
+          *K = fl_sense_K(decltype(ngl)::value, decltype(l)::value, decltype(m)::value);
+        });
+      });
+  }
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_floats_sense(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_floats_sense";
+  auto *s = floats_set(eng, id, who);
+  if (!s) return HNUMO_ERR_INVALID;
+  const int S = fl_sense_rows(s->sensors);
+  if (S == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": float set " + std::to_string(id) + " has no sensors (hnumo_floats_sensors)");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": out is NULL");
+  const int64_t want = (int64_t)S * s->M;
+  if (n != want) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": n must be S*M = " + std::to_string(want) + ", got " + std::to_string(n));
+  if (int rc = floats_sense_refused(eng, *s, who)) return rc;
+  HIPCHK(hipSetDevice(eng->device));
+  // (sized for every sensor: the mask may change)
+  if (!s->d_sense && !alloc_doubles(&s->d_sense, (size_t)fl_sense_rows(FL_SENSE_ALL) * (size_t)s->M)) {
+    (void)hipGetLastError();
+    return fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation failed");
+  }
+  if (int rc = floats_sense_launch(eng, *s, s->d_sense)) return rc;
+  std::vector<double> raw((size_t)want);
+  if (int rc = download(eng, raw.data(), s->d_sense, (size_t)want * sizeof(double))) return rc;
+  sample_transpose(raw.data(), S, (size_t)s->M, 1, out);
+  return HNUMO_OK;
 }
 
 extern "C" int hnumo_floats_destroy(hnumo_engine *eng, int32_t id) {

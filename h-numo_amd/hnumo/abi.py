@@ -97,6 +97,22 @@ class Halo:
         self.desc = h
 
 
+FLOAT_SENSE_STATE, FLOAT_SENSE_VORT = 1, 2    # HNUMO_FLOAT_SENSE_STATE, HNUMO_FLOAT_SENSE_VORT
+
+
+def float_sense_rows(mask: int) -> int:
+    """S: the rows a sensor mask adds to a float set's record."""
+    return (5 if mask & FLOAT_SENSE_STATE else 0) + (4 if mask & FLOAT_SENSE_VORT else 0)
+
+
+def declare_float_sensors(L):
+    """The float sets' sensor calls of the loaded library L (hnumo_floats_sensors, _sense, _sense_info)."""
+    vp, i32 = C.c_void_p, C.c_int32
+    L.hnumo_floats_sensors.argtypes = [vp, i32, i32]
+    L.hnumo_floats_sense.argtypes = [vp, i32, _dp, C.c_int64]
+    L.hnumo_floats_sense_info.argtypes = [vp, i32, _ip, _ip]
+
+
 def ptr(a: np.ndarray | None):
     """Pointer to a contiguous Fortran-order array (keeps no reference: caller owns it)."""
     if a is None:

@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from . import abi
 from . import bundle as _bundle
 from .abi import Descriptors, Halo, HaloDesc
 
@@ -107,6 +108,7 @@ def lib():
         L.hnumo_floats_settle.argtypes = [vp, i32]
         L.hnumo_group_floats_migrate.argtypes = [C.POINTER(vp), C.c_int, i32, i32, C.c_double]
         L.hnumo_group_floats_advance.argtypes = [C.POINTER(vp), C.c_int, i32, C.c_double]
+        abi.declare_float_sensors(L)
         L.hnumo_wind_begin.argtypes = [vp, dp, i64, i32]
         L.hnumo_wind_set.argtypes = [vp, dp, i32]
         L.hnumo_wind_schedule.argtypes = [vp, dp, i32, i32, i32, i32]
@@ -551,8 +553,29 @@ class Engine:
         self._check(lib().hnumo_floats_record(self.h, int(fid)))
 
     def floats_series(self, fid: int, clear: bool = False):
-        """(5, M, count) = x, y, u, v, elem per record; clear empties the series afterwards."""
-        return self._series(lib().hnumo_floats_series, (5, self._set_sizes("float", fid)), int(fid), clear=clear)
+        """(5 + S, M, count) = x, y, u, v, elem and the set's S sensor rows per record; clear empties the
+        series afterwards."""
+        M = self._set_sizes("float", fid)
+        return self._series(lib().hnumo_floats_series, (5 + self.floats_sense_info(fid)[0], M), int(fid), clear=clear)
+
+    def floats_sensors(self, fid: int, mask: int):
+        """The set's sensor mask (abi.FLOAT_SENSE_STATE + abi.FLOAT_SENSE_VORT; 0: none): S rows of the float's
+        own layer behind the 5 of every record.  Sensors first, then floats_begin."""
+        self._check(lib().hnumo_floats_sensors(self.h, int(fid), int(mask)))
+
+    def floats_sense(self, fid: int):
+        """(S, M): the set's sensors on the state on the device now, in input order."""
+        M = self._set_sizes("float", fid)
+        out = np.zeros((self.floats_sense_info(fid)[0], M), order="F")
+        buf = out if out.size else np.zeros(1)
+        self._check(lib().hnumo_floats_sense(self.h, int(fid), _dp(buf), out.size))
+        return out
+
+    def floats_sense_info(self, fid: int):
+        """(S, K): the sensor rows of the set and the element slots of the sensor kernel's arena."""
+        S, K = C.c_int32(), C.c_int32()
+        self._check(lib().hnumo_floats_sense_info(self.h, int(fid), C.byref(S), C.byref(K)))
+        return S.value, K.value
 
     def floats_destroy(self, fid: int):
         self._check(lib().hnumo_floats_destroy(self.h, int(fid)))

@@ -41,7 +41,13 @@ holds it is the single-rank float's, bit for bit, through any number of crossing
 
     HostFloatGroup      the numpy mirror of the group protocol over one HostFloats per rank
     GroupFloats         the same set on the engines of a local group (hnumo_group_floats_*)
-    merge_series        the ranks' series as one, with global element numbers"""
+    merge_series        the ranks' series as one, with global element numbers
+
+Sensors (include/hnumo_engine.h has the normative text): a set's mask SENSE_STATE + SENSE_VORT adds S = 5 + 4
+rows to every record -- h, u, v, dp, elevation and zeta, delta, pv, ow of the float's own layer, each the value
+a hnumo.sample set reads at the float's cached (elem, xi, eta); 0.0 for a float with elem = 0.  HostFloats
+composes them of the existing mirrors (HostSampler, HostVorticity); DeviceFloats reads them from the engine
+(float_sense_kernel), bit for bit the same (tests/test_float_sense_gpu.py)."""
 from __future__ import annotations
 
 import math
@@ -49,6 +55,7 @@ import math
 import numpy as np
 
 from . import sample as _sample
+from .abi import FLOAT_SENSE_STATE as SENSE_STATE, FLOAT_SENSE_VORT as SENSE_VORT, float_sense_rows as sense_rows
 
 ACTIVE, LEFT, LOST = 0, 1, 2      # HNUMO_FLOAT_ACTIVE, HNUMO_FLOAT_LEFT, HNUMO_FLOAT_LOST
 FLIGHT = 3                        # locate's answer at a processor face of a migrating set (never a float's status)
@@ -88,6 +95,18 @@ def side_neighbours(case):
     if (nbr == -3).any():
         raise ValueError("an owned element has a side without a face")
     return nbr
+
+
+def sense_slots(elem):
+    """The slot rule of the sensor kernel for one workgroup's floats `elem` (1-based elements in slot order, <= 0:
+    inactive): (slot (n) with -1 for inactive floats, the 0-based elements of the slots).  A float is a head when
+    it is active and it is the first, or the float before it is inactive or in another element; a slot per head."""
+    elem = np.asarray(elem).reshape(-1)
+    act = elem > 0
+    head = act.copy()
+    head[1:] &= ~act[:-1] | (elem[1:] != elem[:-1])
+    slot = np.where(act, np.cumsum(head) - 1, -1).astype(np.int32)
+    return slot, (elem[head] - 1).astype(np.int32)
 
 
 def _bilinear(c, xi, eta):
@@ -142,8 +161,10 @@ class HostFloats:
 
     needs_host_state = True
 
-    def __init__(self, case, xy, layer, xgl=None, coord=None, coord_scale=0.0):
+    def __init__(self, case, xy, layer, xgl=None, coord=None, coord_scale=0.0, sensors=0, coriolis=True):
         S = case.scalars
+        self.sensors, self.coriolis = 0, coriolis
+        self._q = None                    # the state of the last advance: what record() senses
         self.case = case
         self.ngl, self.L, self.npoin = S["ngl"], S["nlayers"], S["npoin"]
         self.P = self.ngl ** 2
@@ -171,6 +192,38 @@ class HostFloats:
         self.set(xy, layer)
         if coord_scale:
             self.set_coord_scale(coord_scale)
+        self.set_sensors(sensors)
+
+    # ---- sensors
+    def set_sensors(self, mask):
+        """The sensor mask (hnumo_floats_sensors): refused for an unknown bit and while records of another
+        width are held."""
+        mask = int(mask)
+        if mask < 0 or mask & ~(SENSE_STATE | SENSE_VORT):
+            raise ValueError(f"sensors: the mask must be a sum of SENSE_STATE (1) and SENSE_VORT (2), got {mask}")
+        if self._records and sense_rows(mask) != sense_rows(self.sensors):
+            raise ValueError("sensors: the series holds records of another width (series(clear=True) first)")
+        self.sensors = mask
+
+    def sense(self, q_df):
+        """(S, M): the sensor rows of every float at its cached (elem, xi, eta) on q_df (3, npoin, L)."""
+        if not self.sensors:
+            raise ValueError("sense: the set has no sensors")
+        if q_df is None:
+            raise ValueError("sense: no state yet (advance first)")
+        from .vorticity import HostVorticity
+        m, k = np.arange(self.M), self.layer.astype(np.int64) - 1
+        rows = []
+        if self.sensors & SENSE_STATE:
+            hs = _sample.HostSampler(self.case, self.elem, self.xi, self.eta, _sample.STATE, xgl=self.xgl)
+            full = hs.sample(q_df, np.zeros((4, self.npoin)))          # (the qb rows are not taken)
+            rows += [full[5 * k + v, m] for v in range(5)]
+        if self.sensors & SENSE_VORT:
+            hs = _sample.HostSampler(self.case, self.elem, self.xi, self.eta, _sample.VORT, xgl=self.xgl)
+            with np.errstate(all="ignore"):
+                full = hs.sample_vort(HostVorticity(self.case, coriolis=self.coriolis, series=False).fields(q_df))
+            rows += [full[4 * k + v, m] for v in range(4)]
+        return np.asfortranarray(np.stack(rows))
 
     def set_coord_scale(self, scale):
         """tol_e of every later location from max|coord| = scale (0: the case's own again); seeds stay."""
@@ -332,7 +385,7 @@ class HostFloats:
         """One advance of every ACTIVE float by dt (default: the case's dt) on q_df (3, npoin, L).
         Afterwards: hops (M) = the most hops a location of this advance took per float, walled (M) =
         whether a wall moved a target."""
-        q = np.asarray(q_df)
+        q = self._q = np.asarray(q_df)
         dt = float(self.dt if dt is None else dt)
         self.hops = np.zeros(self.M, dtype=np.int32)
         self.walled = np.zeros(self.M, dtype=bool)
@@ -356,6 +409,7 @@ class HostFloats:
         """The tail of an advance from the flight record fl (a dict as in outbox) in this rank's 0-based
         element e behind the face: float_plan.h's float_resume, into slot fl["gid"]."""
         m, k = fl["gid"], fl["layer"] - 1
+        self._q = np.asarray(q_df)
         self.walls = 0
         self._through = self.visited[m]
         self.fresh[m] = 0
@@ -379,10 +433,14 @@ class HostFloats:
                 "elem": self.elem.copy(), "status": self.status.copy()}
 
     def record(self):
-        self._records.append(np.stack([self.x, self.y, self.wx, self.wy, self.elem.astype(np.float64)]))
+        """x, y, u, v, elem and the S sensor rows on the state of the last advance."""
+        rec = np.stack([self.x, self.y, self.wx, self.wy, self.elem.astype(np.float64)])
+        if self.sensors:
+            rec = np.concatenate([rec, self.sense(self._q)])
+        self._records.append(rec)
 
     def series(self, clear: bool = False):
-        out = np.zeros((5, self.M, len(self._records)), order="F")
+        out = np.zeros((5 + sense_rows(self.sensors), self.M, len(self._records)), order="F")
         for i, r in enumerate(self._records):
             out[:, :, i] = r
         if clear:
@@ -397,17 +455,33 @@ class DeviceFloats:
 
     needs_host_state = False
 
-    def __init__(self, engine, xy, layer, xgl=None, coord=None):
+    def __init__(self, engine, xy, layer, xgl=None, coord=None, sensors=0):
         self.engine = engine
         case = engine.case
         self.xy, self.layer = np.asfortranarray(xy, dtype=np.float64), layer
         self.id = engine.floats_create(case.arrays["coord"] if coord is None else coord,
                                        _sample.case_xgl(case) if xgl is None else xgl, self.xy, layer)
         self.every = 0
+        self.sensors = 0
+        if sensors:
+            self.set_sensors(sensors)
 
-    def host_floats(self):
-        """The Python mirror seeded as this set was."""
-        return HostFloats(self.engine.case, self.xy, self.layer)
+    def host_floats(self, coriolis=True):
+        """The Python mirror seeded as this set was, with its sensors."""
+        return HostFloats(self.engine.case, self.xy, self.layer, sensors=self.sensors, coriolis=coriolis)
+
+    def set_sensors(self, mask):
+        """The sensor mask (hnumo_floats_sensors): before begin(); SENSE_VORT after the engine's vort_begin."""
+        self.engine.floats_sensors(self.id, mask)
+        self.sensors = int(mask)
+
+    def sense(self, q_df=None):
+        """(S, M): the sensors on the state on the device now; q_df is ignored."""
+        return self.engine.floats_sense(self.id)
+
+    def sense_info(self):
+        """(S, K): the sensor rows and the element slots of the sensor kernel's arena."""
+        return self.engine.floats_sense_info(self.id)
 
     def set(self, xy, layer):
         self.xy, self.layer = np.asfortranarray(xy, dtype=np.float64), layer
@@ -553,8 +627,8 @@ class HostFloatGroup:
 
 
 def merge_series(series_per_rank, parts):
-    """(5, M, count) from the ranks' series (5, M, count) of one migrating set: for each float and record the
-    rank where elem > 0, its element numbered globally (1-based, through parts[r].elems).  A float no rank
+    """(5 + S, M, count) from the ranks' series (5 + S, M, count) of one migrating set: for each float and record the
+    rank where elem > 0, its element numbered globally (1-based, through parts[r].elems); sensor rows go along.  A float no rank
     holds in a record (it left the domain's ranks, or is LOST) is taken from the rank that held it last, from
     rank 0 if none ever did."""
     sers = [np.asarray(s) for s in series_per_rank]
@@ -582,10 +656,10 @@ class GroupFloats:
     xy, layer on every engine, hnumo_group_floats_migrate, and then begin / advance / get / series / destroy;
     get() and series() return one entry per rank (merge_series joins the series)."""
 
-    def __init__(self, engines, xy, layer, coord_scale=0.0, migrate=True):
+    def __init__(self, engines, xy, layer, coord_scale=0.0, migrate=True, sensors=0):
         from .engine import group_floats_migrate
         self.engines = list(engines)
-        self.sets = [DeviceFloats(e, xy, layer) for e in self.engines]
+        self.sets = [DeviceFloats(e, xy, layer, sensors=sensors) for e in self.engines]
         self.id = self.sets[0].id
         if any(s.id != self.id for s in self.sets):
             raise ValueError("the set must get the same id on every engine of the group")
@@ -637,21 +711,28 @@ def seed_ring(centre, radius: float, n: int, phase: float = 0.0):
     return xy
 
 
-def write_trajectories(path, series, layer, status):
-    """One .npz: series (5, M, count) = x, y, u, v, elem per record, layer (M), status (M)."""
+def write_trajectories(path, series, layer, status, sensors=0):
+    """One .npz: series (5 + S, M, count) = x, y, u, v, elem and the S sensor rows of the mask `sensors` per
+    record, layer (M), status (M); the mask is stored when it is not 0."""
     series = np.asarray(series, dtype=np.float64)
-    if series.ndim != 3 or series.shape[0] != 5:
-        raise ValueError(f"series: shape {series.shape}, expected (5, M, count)")
+    sensors = int(sensors)
+    if sensors < 0 or sensors & ~(SENSE_STATE | SENSE_VORT):
+        raise ValueError(f"sensors: the mask must be a sum of SENSE_STATE (1) and SENSE_VORT (2), got {sensors}")
+    nrows = 5 + sense_rows(sensors)
+    if series.ndim != 3 or series.shape[0] != nrows:
+        raise ValueError(f"series: shape {series.shape}, expected ({nrows}, M, count)")
     M = series.shape[1]
     layer = np.broadcast_to(np.asarray(layer, dtype=np.int32), (M,))
     status = np.asarray(status, dtype=np.int32).reshape(-1)
     if status.size != M:
         raise ValueError(f"status: {status.size} entries, expected {M}")
+    extra = {"sensors": np.int32(sensors)} if sensors else {}
     with open(path, "wb") as f:
-        np.savez(f, series=series, layer=layer, status=status)
+        np.savez(f, series=series, layer=layer, status=status, **extra)
 
 
-def read_trajectories(path):
-    """(series, layer, status) of a write_trajectories file."""
+def read_trajectories(path, with_sensors: bool = False):
+    """(series, layer, status) of a write_trajectories file; with_sensors: and the sensor mask (0: none stored)."""
     with np.load(path) as z:
-        return z["series"], z["layer"], z["status"]
+        out = z["series"], z["layer"], z["status"]
+        return (*out, int(z["sensors"]) if "sensors" in z.files else 0) if with_sensors else out

@@ -93,12 +93,14 @@ module hnumo_engine_c
         hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
         hnumo_floats_begin, hnumo_floats_record, hnumo_floats_series, hnumo_floats_destroy, &
         hnumo_floats_migrate, hnumo_floats_release, hnumo_floats_outbox, hnumo_floats_deliver, hnumo_floats_settle, &
+        hnumo_floats_sensors, hnumo_floats_sense, hnumo_floats_sense_info, &
         hnumo_wind_begin, hnumo_wind_set, hnumo_wind_schedule, hnumo_wind_get, hnumo_wind_end
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
     integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1, &
         HNUMO_SAMPLE_VORT = 2   ! sample set sources
     integer(c_int32_t), parameter, public :: HNUMO_WIND_MAXM = 4, HNUMO_WIND_HOLD = 0, HNUMO_WIND_REPEAT = 1
     integer(c_int32_t), parameter, public :: HNUMO_FLOAT_ACTIVE = 0, HNUMO_FLOAT_LEFT = 1, HNUMO_FLOAT_LOST = 2   ! float status
+    integer(c_int32_t), parameter, public :: HNUMO_FLOAT_SENSE_STATE = 1, HNUMO_FLOAT_SENSE_VORT = 2   ! sensor mask bits
 
     interface
         integer(c_int) function hnumo_engine_create(mesh, statics, params, halo, device, eng) &
@@ -556,6 +558,32 @@ module hnumo_engine_c
             type(c_ptr), value :: eng
             integer(c_int32_t), value :: id
         end function hnumo_floats_settle
+
+        ! sensors: mask = HNUMO_FLOAT_SENSE_STATE + HNUMO_FLOAT_SENSE_VORT adds S = 5 + 4 rows (h, u, v, dp, elevation;
+        ! zeta, delta, pv, ow of the float's own layer) to every record: hnumo_floats_series then returns out(5+S,M,count).
+        ! Sensors first, then hnumo_floats_begin
+        integer(c_int) function hnumo_floats_sensors(eng, id, mask) bind(C, name='hnumo_floats_sensors')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id, mask
+        end function hnumo_floats_sensors
+
+        ! out(S,M) in input order: the sensors on the state on the device now; n = S*M
+        integer(c_int) function hnumo_floats_sense(eng, id, out, n) bind(C, name='hnumo_floats_sense')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_floats_sense
+
+        ! nrows = S; K = the element slots of the sensor kernel's arena for this set (0 without sensors)
+        integer(c_int) function hnumo_floats_sense_info(eng, id, nrows, K) bind(C, name='hnumo_floats_sense_info')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            integer(c_int32_t), intent(out) :: nrows, K
+        end function hnumo_floats_sense_info
 
         ! ---- time-dependent wind stress (hnumo_wind_*, include/hnumo_engine.h): the wind as a linear
         ! combination of M <= HNUMO_WIND_MAXM patterns, formed on the device

@@ -514,6 +514,35 @@ int hnumo_sample_destroy(hnumo_engine *eng, int32_t id);
  *   in input order; n = the doubles out can hold; out = NULL (n = 0) only returns count; clear = 1
  *   empties the series after the copy.
  * hnumo_floats_destroy: frees the set; its id is given out again.
+ *
+ * Sensors (additive in ABI v10): what a float measures on the way.  A set has a sensor mask,
+ * HNUMO_FLOAT_SENSE_STATE (1) + HNUMO_FLOAT_SENSE_VORT (2); the rows are those of the float's own layer k:
+ *   STATE  S1 = 5 rows h, u, v, dp, elevation: rows 5(k-1)+1..5k of a HNUMO_SAMPLE_STATE set;
+ *   VORT   S2 = 4 rows zeta, delta, pv, ow: rows 4(k-1)+1..4k of a HNUMO_SAMPLE_VORT set, f as
+ *          hnumo_vort_begin took it.
+ *   STATE rows come first; S is the sum over the set bits.
+ * The value of a row for a float with elem > 0 is exactly what a hnumo_sample_create_ref set reads in that row
+ * at the float's cached (elem, xi, eta), on the state on the device now: the nodal fields are formed by the
+ * same statements; the weights are w = w*((xi - xgl[m])/(xgl[i] - xgl[m])) in the order of m (the statement
+ * vel uses; hnumo/sample.py's lagrange_weights is its mirror); val = sum_j Ly[j]*(sum_i Lx[i]*F), left to
+ * right from the first product, no FMA.  A float with elem = 0 (LEFT, LOST, not on this rank) reads 0.0 in
+ * every row.  The STATE rows u, v therefore equal the record's own u, v bit for bit after an advance.
+ * hnumo_floats_sensors: sets the mask (0: no sensors).  4 for an unknown id, an unknown bit, the VORT bit
+ *   before hnumo_vort_begin (the rule of a HNUMO_SAMPLE_VORT set), and when the set's series has capacity > 0
+ *   and the mask would change its width: sensors first, then hnumo_floats_begin; to change the mask later,
+ *   begin with capacity 0 first.
+ * hnumo_floats_begin allocates the series at 5 + S rows; hnumo_floats_record and the record that falls due
+ *   after an advance append x, y, u, v, elem and the S sensor rows of the state on the device at that moment
+ *   (after a step: the new time level at the new position; in a group: after the last round of arrivals, on
+ *   the rank that holds the float); hnumo_floats_series returns out(5+S,M,count).
+ * hnumo_floats_sense: the sensors now, out(S,M) in input order, n = S*M.  4 for S = 0, before any state was
+ *   uploaded, and when the mask holds VORT and hnumo_vort_end has been called.  A record meets the same
+ *   refusals; one that falls due is then reported like a full series: the step and the advance are done, the
+ *   other observers still run and the first non-zero code is returned.
+ * hnumo_floats_sense_info: S and K, the element slots the sensor kernel's arena holds for this set (0 without
+ *   sensors); either pointer may be NULL.
+ * A set whose mask is 0 is the set described above: the same launches, series width, bytes and messages.
+ *
  * All launches are plain launches on the engine stream outside the captured step: the step's
  * launches, graph and bits are the same with or without sets.  All return 4, with a message in
  * hnumo_last_error, for an unknown id, a wrong M or n, invalid arguments or geometry, a ninth set;
@@ -538,6 +567,11 @@ int hnumo_floats_outbox(hnumo_engine *eng, int32_t id, double *d, int32_t *i, in
 int hnumo_floats_deliver(hnumo_engine *eng, int32_t id, int32_t src_rank, const double *d, const int32_t *i, int64_t cap,
                          int64_t n);
 int hnumo_floats_settle(hnumo_engine *eng, int32_t id);
+#define HNUMO_FLOAT_SENSE_STATE 1
+#define HNUMO_FLOAT_SENSE_VORT 2
+int hnumo_floats_sensors(hnumo_engine *eng, int32_t id, int32_t mask);
+int hnumo_floats_sense(hnumo_engine *eng, int32_t id, double *out, int64_t n);
+int hnumo_floats_sense_info(hnumo_engine *eng, int32_t id, int32_t *nrows, int32_t *K);
 
 /* Time-dependent wind stress (additive in ABI v10; no reference counterpart: the reference sets
  * tau_wind once, initial_conditions.F90:190, and reads it as plain data).  A few wind patterns are
