@@ -6,9 +6,9 @@
 // ~20 baroclinic kernels) is captured once into a hipGraph and replayed.  The run diagnostics of
 // the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) and the
 // online flow statistics (kernels_stats.hip: hnumo_stats_*), the vorticity products (kernels_vort.hip:
-// hnumo_vort_*), the sample sets (kernels_sample.hip) and the float sets (kernels_float.hip:
-// hnumo_floats_*) are plain launches on the same stream between replays; the host side of those four
-// observers is observers.hip, included below.
+// hnumo_vort_*), the eddy covariances (kernels_cov.hip: hnumo_cov_*), the sample sets
+// (kernels_sample.hip) and the float sets (kernels_float.hip: hnumo_floats_*) are plain launches on the
+// same stream between replays; the host side of those five observers is observers.hip, included below.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -36,6 +36,7 @@
 #include "kernels_diag.hip"
 #include "kernels_stats.hip"
 #include "kernels_vort.hip"
+#include "kernels_cov.hip"
 #include "kernels_sample.hip"
 #include "kernels_float.hip"
 #include "kernels_wind.hip"
@@ -227,6 +228,16 @@ struct hnumo_engine {
     TreeSum tree;
     Series series;
   } vort;
+  // eddy covariances (hnumo_cov_begin .. hnumo_cov_end; kernels_cov.hip): the caller's coriolis_df and
+  // zref (NULL: 0), the running sums [L][7][npoin] pairs, the samples taken, `every` and the steps
+  // counted for it, the element partials [3L][ne] with their tree and the integrals [3L]
+  struct Cov {
+    bool on = false;
+    double *f = nullptr, *zref = nullptr, *sums = nullptr, *integ = nullptr;
+    int64_t nsamples = 0, steps = 0;
+    int every = 0;
+    TreeSum tree;
+  } cov;
   // sample sets (hnumo_sample_*): the host plan (sample_plan.h), its tables on the device, one
   // sample's output [V][M]
   struct SampleSet {
@@ -1610,6 +1621,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   if (eng->h_diag) (void)hipHostFree(eng->h_diag);
   stats_free(eng);
   vort_free(eng);
+  cov_free(eng);
   for (int id = 0; id < SP_MAXSETS; id++) sample_free(eng, id);
   for (int id = 0; id < FL_MAXSETS; id++) floats_free(eng, id);
   wind_free(eng);

@@ -17,6 +17,8 @@
 //                 at once, pv, ow into registers), barrier, the two rows.  The passes have the same trip count on every lane, so the barriers
 //                 are reached by all; a station set costs its own few elements, not a pass over the
 //                 field
+//   source COV    V = 16L: the 16 fields of layer k as cov_node_fields (kernels_cov.hip) forms them from
+//                 the covariances' sums and sample count (SampleArgs::sums, nsamp hold those then)
 // Value: val = sum_j Ly[j] * r_j, r_j = sum_i Lx[i] * F(e, j*ngl + i), both sums left to right from
 // their first product.  Points without an element read 0.0.  Built with -ffp-contract=off: no FMA;
 // the host mirror is hnumo/sample.py (HostSampler), equal bit for bit.
@@ -49,9 +51,10 @@ struct SampleArgs {
 };
 
 // (the VORT source holds D, h and pv, ow across its barriers: four workgroups per CU leave it the
-// registers for that without scratch at NGL = 8, L = 3; the other sources keep five)
+// registers for that without scratch at NGL = 8, L = 3; three leave the COV source those for its seven
+// pairs and 16 fields per layer without scratch at NGL = 6; the other sources keep five)
 template <int NGL, int L, int SRC>
-__global__ void __launch_bounds__(SP_CHUNK, SRC == SP_SRC_VORT ? 4 : 5) sample_kernel(SampleArgs a) {
+__global__ void __launch_bounds__(SP_CHUNK, SRC == SP_SRC_COV ? 3 : SRC == SP_SRC_VORT ? 4 : 5) sample_kernel(SampleArgs a) {
   constexpr int P = NGL * NGL, V = sp_nval(L, SRC), ES = sp_estride(NGL, V), K = sp_K(NGL, V);
   static_assert(K >= 1, "the arena holds no element");
   __shared__ double s_f[K * ES];
@@ -122,7 +125,15 @@ __global__ void __launch_bounds__(SP_CHUNK, SRC == SP_SRC_VORT ? 4 : 5) sample_k
     const int le = t / P, ln = t - le * P;
     const size_t I = (size_t)a.el_list[el0 + le] * P + ln;
     double *s = s_f + le * ES + ln;
-    if (SRC == SP_SRC_STATE) {
+    if (SRC == SP_SRC_COV) {
+#pragma unroll
+      for (int k = 0; k < L; k++) {
+        double f[CV_NFIELD];
+        cov_node_fields(a.sums, k, I, npoin, a.nsamp, f);
+#pragma unroll
+        for (int v = 0; v < CV_NFIELD; v++) s[(CV_NFIELD * k + v) * P] = f[v];
+      }
+    } else if (SRC == SP_SRC_STATE) {
       double f[L][5];
       diag_layer_fields<L>(a.q, ag, a.zbot[I], I, npoin, f);
 #pragma unroll

@@ -1,13 +1,15 @@
 // observers.hip -- what runs after a successful step of the resident state: the online flow
-// statistics (kernels_stats.hip), the vorticity products (kernels_vort.hip), the sample sets
-// (kernels_sample.hip, sample_plan.h) and the float sets (kernels_float.hip, float_plan.h).
+// statistics (kernels_stats.hip), the vorticity products (kernels_vort.hip), the eddy covariances
+// (kernels_cov.hip), the sample sets (kernels_sample.hip, sample_plan.h) and the float sets
+// (kernels_float.hip, float_plan.h).
 //
 // Part of engine.hip's translation unit: included there once fail, HIPCHK and struct hnumo_engine
 // (with Series and TreeSum) are defined.  All of it is plain launches on the engine stream outside
 // the captured step: the step's launches, graph and bits are the same with or without observers.
 //
 // An observer is a kernel, a Series, an entry in observers_after_step and a free in
-// hnumo_engine_destroy; the pieces below are what the four have in common.
+// hnumo_engine_destroy; the pieces below are what the five have in common (the eddy covariances keep
+// no series: their `every` stands alone).
 
 // ------------------------------------------------------------------ shared pieces
 // eng->L and eng->ngl as compile-time constants for a generic lambda (unsupported values are
@@ -439,6 +441,205 @@ extern "C" int hnumo_vort_series(hnumo_engine *eng, double *out, int64_t n, int6
   return series_read(eng, eng->vort.series, 0, 0, out, n, count, clear, "hnumo_vort_series", "3*nlayers");
 }
 
+// ------------------------------------------------------------------ eddy covariances
+// eng->cov: the caller's coriolis_df and zref (NULL: 0), the running sums [L][7][npoin] pairs, the
+// element partials [3L][ne] of the integrals with their tree and the integrals [3L]; nsamples: samples
+// taken since begin.  No series: `every` and `steps` alone say when a sample is due after a step
+static void cov_free(hnumo_engine *eng) {
+  auto &cv = eng->cov;
+  dfree(cv.f, cv.zref, cv.sums, cv.integ);
+  tree_free(cv.tree);
+  cv.on = false;
+  cv.nsamples = cv.steps = 0;
+  cv.every = 0;
+}
+
+static size_t cov_nsums(const hnumo_engine *eng) { return CV_NSUM * (size_t)eng->npoin * eng->L; }
+
+// L = 2 or 3 as a compile-time constant (hnumo_cov_begin refuses the rest)
+template <class F>
+static void cov_with_L(int L, F &&f) {
+  if (L == 2)
+    f(std::integral_constant<int, 2>{});
+  else
+    f(std::integral_constant<int, 3>{});
+}
+
+extern "C" int hnumo_cov_begin(hnumo_engine *eng, const double *coriolis_df, const double *zref, int32_t every) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (every < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_begin: every must be >= 0, got " + std::to_string(every));
+  if (eng->L < 2 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_begin: unsupported nlayers or ngl (nlayers 2 or 3; ngl 3, 4, 5, 6 or 8), got " +
+                                            std::to_string(eng->L) + ", " + std::to_string(eng->ngl));
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
+  cov_free(eng);
+  auto &cv = eng->cov;
+  const size_t npoin = (size_t)eng->npoin;
+  bool ok = alloc_doubles(&cv.sums, cov_nsums(eng)) && alloc_doubles(&cv.integ, (size_t)CV_NINT * eng->L) &&
+            tree_alloc(cv.tree, CV_NINT * eng->L, eng->nelem_owned) && (!coriolis_df || alloc_doubles(&cv.f, npoin)) &&
+            (!zref || alloc_doubles(&cv.zref, npoin * eng->L));
+  if (ok && coriolis_df) ok = hipMemcpy(cv.f, coriolis_df, npoin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && zref) ok = hipMemcpy(cv.zref, zref, npoin * eng->L * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    cov_free(eng);
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_cov_begin: device allocation or upload failed");
+  }
+  // (the nodes of ghost elements are never accumulated: their sums stay +0.0)
+  HIPCHK(hipMemsetAsync(cv.sums, 0, cov_nsums(eng) * sizeof(double), eng->stream));
+  cv.every = every;
+  cv.on = true;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_cov_end(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->cov.on) return HNUMO_OK;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  cov_free(eng);
+  return HNUMO_OK;
+}
+
+static CovArgs cov_args(hnumo_engine *eng) {
+  auto &cv = eng->cov;
+  CovArgs a{};
+  a.q = eng->q;
+  a.alpha = eng->alpha;
+  a.nstat = eng->nstat;
+  a.f = cv.f;
+  a.zref = cv.zref;
+  a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
+  a.sums = (double2 *)cv.sums;
+  a.part = cv.tree.part;
+  a.gravity = eng->p.gravity;
+  a.nsamp = (double)cv.nsamples;
+  a.npoin = eng->npoin;
+  a.ne = eng->nelem_owned;
+  a.ngl = eng->ngl;
+  return a;
+}
+
+// one sample of the state on the device, ordered after what is on the engine stream; no copy back
+static int cov_sample(hnumo_engine *eng, const char *who) {
+  auto &cv = eng->cov;
+  if (!cv.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_cov_begin first");
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  const int ne = eng->nelem_owned, EPB = CV_BS / eng->P;
+  if (ne > 0) {
+    const CovArgs a = cov_args(eng);
+    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    with_ngl(eng->ngl, [&](auto ngl) {
+      cov_with_L(eng->L, [&](auto l) {
+        constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
+        hipLaunchKernelGGL((cov_accumulate_kernel<NGL, L>), dim3(nb), dim3(CV_BS), 0, eng->stream, a);
+      });
+    });
+    HIPCHK(hipGetLastError());
+  }
+  cv.nsamples++;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_cov_accumulate(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return cov_sample(eng, "hnumo_cov_accumulate");
+}
+
+// the sums between the device layout [L][7][npoin][2] and the caller's (14,npoin,L)
+extern "C" int hnumo_cov_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_sums: call hnumo_cov_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_sums: out is NULL");
+  const size_t want = cov_nsums(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_sums: n must be 14*npoin*nlayers = " + std::to_string(want) + ", got " +
+                                            std::to_string(n));
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  if (int rc = download(eng, raw.data(), eng->cov.sums, want * sizeof(double))) return rc;
+  for (int k = 0; k < eng->L; k++)
+    for (int p = 0; p < CV_NPAIR; p++)
+      for (size_t I = 0; I < npoin; I++)
+        for (int j = 0; j < 2; j++) out[CV_NSUM * (I + npoin * k) + 2 * p + j] = raw[2 * cv_pair(k, p, I, npoin) + j];
+  if (nsamples) *nsamples = eng->cov.nsamples;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_cov_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: call hnumo_cov_begin first");
+  if (!in) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: in is NULL");
+  const size_t want = cov_nsums(eng), npoin = (size_t)eng->npoin;
+  if (n != (int64_t)want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: n must be 14*npoin*nlayers = " + std::to_string(want) + ", got " +
+                                            std::to_string(n));
+  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: nsamples must be >= 0");
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  for (int k = 0; k < eng->L; k++)
+    for (int p = 0; p < CV_NPAIR; p++)
+      for (size_t I = 0; I < npoin; I++)
+        for (int j = 0; j < 2; j++) raw[2 * cv_pair(k, p, I, npoin) + j] = in[CV_NSUM * (I + npoin * k) + 2 * p + j];
+  HIPCHK(hipMemcpyAsync(eng->cov.sums, raw.data(), want * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  eng->cov.nsamples = nsamples;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_cov_fields(hnumo_engine *eng, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: call hnumo_cov_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: out is NULL");
+  const int64_t want = CV_NFIELD * (int64_t)eng->npoin * eng->L;
+  if (n != want)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: n must be 16*npoin*nlayers = " + std::to_string(want) + ", got " +
+                                            std::to_string(n));
+  if (eng->cov.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: no samples yet");
+  HIPCHK(hipSetDevice(eng->device));
+  double *d = nullptr;
+  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
+  const size_t npoin = (size_t)eng->npoin, nown = (size_t)eng->nelem_owned * eng->P;
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((npoin + CV_BS - 1) / CV_BS, 4096));
+  const double2 *s = (const double2 *)eng->cov.sums;
+  const double ns = (double)eng->cov.nsamples;
+  cov_with_L(eng->L, [&](auto l) {
+    hipLaunchKernelGGL(cov_fields_kernel<decltype(l)::value>, dim3(nb), dim3(CV_BS), 0, eng->stream, s, npoin, nown, ns, d);
+  });
+  const int rc = download(eng, out, d, (size_t)want * sizeof(double));
+  (void)hipFree(d);
+  return rc;
+}
+
+// out(3,nlayers): the element partials, then the tree of the statistics' series
+extern "C" int hnumo_cov_integrals(hnumo_engine *eng, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: call hnumo_cov_begin first");
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: out is NULL");
+  const int rows = CV_NINT * eng->L;
+  if (n != rows)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: n must be 3*nlayers = " + std::to_string(rows) + ", got " +
+                                            std::to_string(n));
+  if (eng->cov.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: no samples yet");
+  HIPCHK(hipSetDevice(eng->device));
+  const int ne = eng->nelem_owned, EPB = CV_BS / eng->P;
+  if (ne == 0) {
+    for (int r = 0; r < rows; r++) out[r] = 0.0;
+    return HNUMO_OK;
+  }
+  const CovArgs a = cov_args(eng);
+  const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+  cov_with_L(eng->L, [&](auto l) {
+    hipLaunchKernelGGL(cov_integrals_kernel<decltype(l)::value>, dim3(nb), dim3(CV_BS), 0, eng->stream, a);
+  });
+  tree_sum(eng, eng->cov.tree, rows, ne, eng->cov.integ);
+  HIPCHK(hipGetLastError());
+  return download(eng, out, eng->cov.integ, (size_t)rows * sizeof(double));
+}
+
 // ------------------------------------------------------------------ sample sets
 // eng->samples[]: the host plan (sample_plan.h), its tables on the device, one sample's output [V][M]
 // and the series [capacity][V][M]
@@ -499,11 +700,13 @@ static int sample_adopt(hnumo_engine *eng, SamplePlan &pl, const double *xgl, in
 
 static int sample_create_checks(hnumo_engine *eng, int32_t source, const int32_t *id, const char *who) {
   if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
-  if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS && source != HNUMO_SAMPLE_VORT)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS or " +
-                                            "HNUMO_SAMPLE_VORT, got " + std::to_string(source));
+  if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS && source != HNUMO_SAMPLE_VORT && source != HNUMO_SAMPLE_COV)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS, " +
+                                            "HNUMO_SAMPLE_VORT or HNUMO_SAMPLE_COV, got " + std::to_string(source));
   if (source == HNUMO_SAMPLE_VORT && !eng->vort.on)
     return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": a set on the vorticity products needs f: call hnumo_vort_begin first");
+  if (source == HNUMO_SAMPLE_COV && !eng->cov.on)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the eddy covariances: call hnumo_cov_begin first");
   if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
     return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
   return 0;
@@ -549,6 +752,10 @@ static int sample_now(hnumo_engine *eng, const SampleSet &s, double *dst, const 
   }
   if (s.source == HNUMO_SAMPLE_VORT && !eng->vort.on)
     return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the vorticity products, which need f: call hnumo_vort_begin first");
+  if (s.source == HNUMO_SAMPLE_COV) {
+    if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the eddy covariances: call hnumo_cov_begin first");
+    if (eng->cov.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the eddy covariances have no samples yet");
+  }
   SampleArgs a{};
   a.nstat = eng->nstat;
   a.f = eng->vort.f;
@@ -570,6 +777,19 @@ static int sample_now(hnumo_engine *eng, const SampleSet &s, double *dst, const 
   a.npoin = (size_t)eng->npoin;
   a.M = (size_t)s.plan.M;
   const int nch = s.plan.nchunks();
+  if (s.source == HNUMO_SAMPLE_COV) {
+    // (the fields of the covariances' own sums and sample count, as STATS reads the statistics')
+    a.sums = (const double2 *)eng->cov.sums;
+    a.nsamp = (double)eng->cov.nsamples;
+    with_ngl(eng->ngl, [&](auto ngl) {
+      cov_with_L(eng->L, [&](auto l) {
+        constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
+        hipLaunchKernelGGL((sample_kernel<NGL, L, SP_SRC_COV>), dim3(nch), dim3(SP_CHUNK), 0, eng->stream, a);
+      });
+    });
+    HIPCHK(hipGetLastError());
+    return HNUMO_OK;
+  }
   with_ngl(eng->ngl, [&](auto ngl) {
     with_L(eng->L, [&](auto l) {
       constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
@@ -1314,8 +1534,9 @@ extern "C" int hnumo_floats_settle(hnumo_engine *eng, int32_t id) {
 
 // ------------------------------------------------------------------ after a successful step
 // Called once run_steps has returned 0 (so a step redone on per-stage launches is observed once), in
-// this order: the statistics' sample; the vorticity series' sample; the sample sets' recordings, which
-// see the new sums of a set on the statistics; the float sets' advance by params.dt, last.  Every
+// this order: the statistics' sample; the vorticity series' sample; the eddy covariances' sample; the
+// sample sets' recordings, which see the new sums of a set on the statistics or the covariances; the
+// float sets' advance by params.dt, last.  Every
 // observer runs whatever the others return (a float cannot skip a step because a series was full);
 // the first non-zero code is returned.
 static int observers_after_step(hnumo_engine *eng) {
@@ -1327,6 +1548,8 @@ static int observers_after_step(hnumo_engine *eng) {
     run(stats_sample(eng, "flow statistics after the step (the step itself succeeded)"));
   if (eng->vort.on && eng->vort.series.cap > 0 && series_due(eng->vort.series))
     run(vort_form(eng, true, "vorticity series after the step (the step itself succeeded)"));
+  if (eng->cov.on && eng->cov.every > 0 && ++eng->cov.steps % eng->cov.every == 0)
+    run(cov_sample(eng, "eddy covariances after the step (the step itself succeeded)"));
   for (int id = 0; id < SP_MAXSETS; id++) {
     auto &s = eng->samples[id];
     if (s.used && series_due(s.series)) run(sample_record(eng, s, id, "sample series after the step (the step itself succeeded)"));

@@ -36,12 +36,13 @@ constexpr int SP_LDS_BYTES = 32768;    // the kernel's LDS arena: five workgroup
 constexpr int SP_MAXSETS = 8;
 constexpr int SP_SRC_STATE = 0, SP_SRC_STATS = 1;   // HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS
 constexpr int SP_SRC_VORT = 2;                      // HNUMO_SAMPLE_VORT
+constexpr int SP_SRC_COV = 3;                       // HNUMO_SAMPLE_COV
 constexpr int SP_ERR_INVALID = 4;                   // HNUMO_ERR_INVALID
 
 // values per point, doubles per element in the arena (an odd count: consecutive element slots
 // start on different LDS banks) and the element slots K of the arena
 constexpr int sp_nval(int L, int source) {
-  return source == SP_SRC_VORT ? 4 * L : source == SP_SRC_STATS ? 5 * L : 5 * L + 4;
+  return source == SP_SRC_COV ? 16 * L : source == SP_SRC_VORT ? 4 * L : source == SP_SRC_STATS ? 5 * L : 5 * L + 4;
 }
 constexpr int sp_estride(int ngl, int V) { return (V * ngl * ngl) | 1; }
 constexpr int sp_K(int ngl, int V) { return SP_LDS_BYTES / (8 * sp_estride(ngl, V)); }

@@ -113,6 +113,18 @@ def declare_float_sensors(L):
     L.hnumo_floats_sense_info.argtypes = [vp, i32, _ip, _ip]
 
 
+def declare_cov(L):
+    """The eddy covariances' calls of the loaded library L (hnumo_cov_*)."""
+    vp, i64 = C.c_void_p, C.c_int64
+    L.hnumo_cov_begin.argtypes = [vp, _dp, _dp, C.c_int32]
+    L.hnumo_cov_accumulate.argtypes = [vp]
+    L.hnumo_cov_sums.argtypes = [vp, _dp, i64, C.POINTER(i64)]
+    L.hnumo_cov_set_sums.argtypes = [vp, _dp, i64, i64]
+    L.hnumo_cov_fields.argtypes = [vp, _dp, i64]
+    L.hnumo_cov_integrals.argtypes = [vp, _dp, i64]
+    L.hnumo_cov_end.argtypes = [vp]
+
+
 def ptr(a: np.ndarray | None):
     """Pointer to a contiguous Fortran-order array (keeps no reference: caller owns it)."""
     if a is None:

@@ -282,7 +282,7 @@ def restart_state(case, path):
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
               time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1, floats=None,
-              vorticity=None, vort_every=1, wind=None):
+              vorticity=None, vort_every=1, wind=None, eddy_cov=None, cov_every=1):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
@@ -316,7 +316,15 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     with n the number of steps of the run taken so far (a restarted loop starts at restart_file_number
     snapshots' worth of steps, so the schedule resumes where the run stopped).  The device object installs
     its schedule on the engine at the first call and does nothing afterwards; the host object hands the
-    blended wind to a stepper that has set_tau_wind.  None: nothing changes."""
+    blended wind to a stepper that has set_tau_wind.  None: nothing changes.
+
+    eddy_cov: a hnumo.covariance.DeviceEddyCov or HostEddyCov, handled as flow_stats is: after every
+    cov_every-th step of this loop (after flow_stats' and the vorticity's sample, before the floats) it
+    gets add(q).  The device object (begun with every = 0) samples the engine's state where it lives (q
+    is ignored, no sync); the host object reads the host arrays, which a resident stepper syncs for it
+    first.  None: nothing changes."""
+    if eddy_cov is not None and int(cov_every) < 1:
+        raise ValueError("cov_every must be >= 1")
     if vorticity is not None and int(vort_every) < 1:
         raise ValueError("vort_every must be >= 1")
     float_sets = [] if floats is None else list(floats) if isinstance(floats, (list, tuple)) else [floats]
@@ -390,6 +398,10 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
             if resident:
                 stepper.sync(q, qb, qp)
             vorticity.add(q)
+        if eddy_cov is not None and nstep % int(cov_every) == 0:
+            if resident and getattr(eddy_cov, "needs_host_state", True):
+                stepper.sync(q, qb, qp)
+            eddy_cov.add(q)
         for fs in float_sets:
             if resident and getattr(fs, "needs_host_state", True):
                 stepper.sync(q, qb, qp)

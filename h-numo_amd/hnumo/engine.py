@@ -109,6 +109,7 @@ def lib():
         L.hnumo_group_floats_migrate.argtypes = [C.POINTER(vp), C.c_int, i32, i32, C.c_double]
         L.hnumo_group_floats_advance.argtypes = [C.POINTER(vp), C.c_int, i32, C.c_double]
         abi.declare_float_sensors(L)
+        abi.declare_cov(L)
         L.hnumo_wind_begin.argtypes = [vp, dp, i64, i32]
         L.hnumo_wind_set.argtypes = [vp, dp, i32]
         L.hnumo_wind_schedule.argtypes = [vp, dp, i32, i32, i32, i32]
@@ -134,6 +135,7 @@ SUMMATION = {"reference": 0, "factored": 1}   # HNUMO_SUM_REFERENCE / HNUMO_SUM_
 DIAG_MASS = 1                                 # HNUMO_DIAG_MASS
 SAMPLE_STATE, SAMPLE_STATS = 0, 1             # HNUMO_SAMPLE_STATE / HNUMO_SAMPLE_STATS
 SAMPLE_VORT = 2                               # HNUMO_SAMPLE_VORT
+SAMPLE_COV = 3                                # HNUMO_SAMPLE_COV
 
 
 def unpack_diagnostics(out, L: int) -> dict:
@@ -434,9 +436,62 @@ class Engine:
     def vort_end(self):
         self._check(lib().hnumo_vort_end(self.h))
 
+    # ---- eddy covariances of the device state (hnumo_cov_*; mirror: hnumo/covariance.py)
+    def cov_begin(self, coriolis_df=None, zref=None, every: int = 0):
+        """Allocate and zero the running sums (again: reset).  coriolis_df (npoin), or None: f = 0; zref
+        (npoin, nlayers), or None: 0.  every = k >= 1: the engine samples itself after every k-th
+        successful step."""
+        npoin, L = self.dims["npoin"], self.dims["nlayers"]
+        fp = zp = None
+        if coriolis_df is not None:
+            f = np.ascontiguousarray(np.asarray(coriolis_df, dtype=np.float64).reshape(-1))
+            if f.size != npoin:
+                raise ValueError(f"coriolis_df: {f.size} elements, expected {npoin}")
+            fp = f.ctypes.data_as(C.POINTER(C.c_double))
+        if zref is not None:
+            z = np.array(zref, dtype=np.float64, order="F")
+            if z.shape != (npoin, L):
+                raise ValueError(f"zref: shape {z.shape}, expected (npoin, nlayers) = ({npoin}, {L})")
+            zp = z.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(lib().hnumo_cov_begin(self.h, fp, zp, int(every)))
+
+    def cov_accumulate(self):
+        """One sample of the state on the device; nothing is copied back."""
+        self._check(lib().hnumo_cov_accumulate(self.h))
+
+    def cov_sums(self):
+        """(sums (14, npoin, nlayers) in the order of covariance.SUM_NAMES; the sample count)."""
+        out = np.zeros((14, self.dims["npoin"], self.dims["nlayers"]), order="F")
+        n = C.c_int64()
+        self._check(lib().hnumo_cov_sums(self.h, _dp(out), out.size, C.byref(n)))
+        return out, n.value
+
+    def cov_set_sums(self, sums, nsamples: int):
+        """Restore sums (14, npoin, nlayers) and a sample count, e.g. of a run being restarted."""
+        a = np.array(sums, dtype=np.float64, order="F")
+        size = 14 * self.dims["npoin"] * self.dims["nlayers"]
+        self._check(lib().hnumo_cov_set_sums(self.h, _dp(a, size, "sums"), a.size, int(nsamples)))
+
+    def cov_fields(self):
+        """(16, npoin, nlayers) in the order of covariance.FIELD_NAMES, of the samples so far."""
+        out = np.zeros((16, self.dims["npoin"], self.dims["nlayers"]), order="F")
+        self._check(lib().hnumo_cov_fields(self.h, _dp(out), out.size))
+        return out
+
+    def cov_integrals(self):
+        """(3, nlayers): the integrals of hbar*(0.5*(Ruu+Rvv)), dvar and hbar*ens over the owned elements."""
+        out = np.zeros((3, self.dims["nlayers"]), order="F")
+        self._check(lib().hnumo_cov_integrals(self.h, _dp(out), out.size))
+        return out
+
+    def cov_end(self):
+        self._check(lib().hnumo_cov_end(self.h))
+
     # ---- sample sets on the device state (hnumo_sample_*; mirror and helpers: hnumo/sample.py)
     def _sample_nval(self, source: int) -> int:
         L = self.dims["nlayers"]
+        if source == SAMPLE_COV:
+            return 16 * L
         return 4 * L if source == SAMPLE_VORT else 5 * L if source == SAMPLE_STATS else 5 * L + 4
 
     def sample_create(self, coord, xgl, xy, source: int = 0) -> int:

@@ -21,6 +21,7 @@ the order of m; Ly[j] from eta likewise.  Nodal fields of element e, node I = e*
            forms them, rows 5L..5L+3 = qb_df(1:4, I)
     STATS  V = 5L: hbar, um, vm, mke, eke of flowstats' fields per layer
     VORT   V = 4L: zeta, delta, pv, ow of vorticity's fields per layer
+    COV    V = 16L: the 16 fields of covariance's fields per layer
 
 Value: val = sum_j Ly[j] * r_j with r_j = sum_i Lx[i] * F(e, j*ngl + i), both sums left to right
 from their first product.  Points with elem = 0 read 0.0 in every row.  At xi = xgl[a], eta =
@@ -36,6 +37,13 @@ from . import diagnostics as _diag
 
 STATE, STATS = 0, 1   # HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS
 VORT = 2              # HNUMO_SAMPLE_VORT
+COV = 3               # HNUMO_SAMPLE_COV
+SOURCES = {"state": STATE, "stats": STATS, "vort": VORT, "cov": COV}
+
+
+def source_id(source) -> int:
+    """A source given by name ("state", "stats", "vort", "cov") or by its number."""
+    return SOURCES[source] if isinstance(source, str) else int(source)
 
 
 def lagrange_weights(xgl, x):
@@ -55,6 +63,9 @@ def lagrange_weights(xgl, x):
 
 
 def nval(nlayers: int, source: int) -> int:
+    source = source_id(source)
+    if source == COV:
+        return 16 * nlayers
     return 4 * nlayers if source == VORT else 5 * nlayers if source == STATS else 5 * nlayers + 4
 
 
@@ -74,7 +85,7 @@ class HostSampler:
 
     def __init__(self, case, elem, xi, eta, source: int = STATE, xgl=None):
         S = case.scalars
-        self.case, self.source = case, source
+        self.case, self.source = case, source_id(source)
         self.ngl, self.L, self.npoin = S["ngl"], S["nlayers"], S["npoin"]
         self.P = self.ngl ** 2
         self.elem = np.asarray(elem, dtype=np.int64).reshape(-1)
@@ -107,7 +118,7 @@ class HostSampler:
         return out
 
     def _rows(self, f5):
-        """(5 or 4, npoin, L) -> (5L or 4L, npoin): layer after layer"""
+        """(5, 4 or 16, npoin, L) -> (5L, 4L or 16L, npoin): layer after layer"""
         return np.concatenate([f5[:, :, k] for k in range(self.L)], axis=0)
 
     def sample_vort(self, fields):
@@ -122,12 +133,17 @@ class HostSampler:
     def sample_stats(self, fields):
         return self._interp(self._rows(np.asarray(fields)))
 
+    def sample_cov(self, fields):
+        """(16L, M) from covariance's fields (16, npoin, L) = HostEddyCov.fields()."""
+        return self._interp(self._rows(np.asarray(fields)))
+
 
 class DeviceSampler:
     """The same read-outs from an hnumo.engine.Engine.  Give either xy (2, M) physical points, which
     the engine locates in its owned elements from the case's coord, or elem (M) with xi_eta (2, M)."""
 
     def __init__(self, engine, xy=None, elem=None, xi_eta=None, source: int = STATE, xgl=None, coord=None):
+        source = source_id(source)
         self.engine, self.source = engine, source
         case = engine.case
         xgl = case_xgl(case) if xgl is None else xgl
@@ -150,7 +166,7 @@ class DeviceSampler:
         """(V, M) of the state (or statistics) on the device now; the arguments are ignored."""
         return self.engine.sample(self.id)
 
-    sample_stats = sample
+    sample_stats = sample_cov = sample
 
     def series_begin(self, every: int = 0, capacity: int = 0):
         self.engine.sample_series_begin(self.id, every, capacity)

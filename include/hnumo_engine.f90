@@ -88,6 +88,8 @@ module hnumo_engine_c
         hnumo_layer_fields, hnumo_stats_begin, hnumo_stats_accumulate, hnumo_stats_sums, &
         hnumo_stats_set_sums, hnumo_stats_fields, hnumo_stats_series, hnumo_stats_end, &
         hnumo_vort_begin, hnumo_vort_fields, hnumo_vort_record, hnumo_vort_series, hnumo_vort_end, &
+        hnumo_cov_begin, hnumo_cov_accumulate, hnumo_cov_sums, hnumo_cov_set_sums, hnumo_cov_fields, &
+        hnumo_cov_integrals, hnumo_cov_end, &
         hnumo_sample_create, hnumo_sample_create_ref, hnumo_sample_plan, hnumo_sample, &
         hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy, &
         hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
@@ -97,7 +99,7 @@ module hnumo_engine_c
         hnumo_wind_begin, hnumo_wind_set, hnumo_wind_schedule, hnumo_wind_get, hnumo_wind_end
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
     integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1, &
-        HNUMO_SAMPLE_VORT = 2   ! sample set sources
+        HNUMO_SAMPLE_VORT = 2, HNUMO_SAMPLE_COV = 3   ! sample set sources
     integer(c_int32_t), parameter, public :: HNUMO_WIND_MAXM = 4, HNUMO_WIND_HOLD = 0, HNUMO_WIND_REPEAT = 1
     integer(c_int32_t), parameter, public :: HNUMO_FLOAT_ACTIVE = 0, HNUMO_FLOAT_LEFT = 1, HNUMO_FLOAT_LOST = 2   ! float status
     integer(c_int32_t), parameter, public :: HNUMO_FLOAT_SENSE_STATE = 1, HNUMO_FLOAT_SENSE_VORT = 2   ! sensor mask bits
@@ -358,6 +360,61 @@ module hnumo_engine_c
             type(c_ptr), value :: eng
         end function hnumo_vort_end
 
+        ! Eddy covariances on the device state (see include/hnumo_engine.h): Reynolds stresses, eddy
+        ! thickness flux, interface / SSH variance, eddy PV flux and eddy potential enstrophy from 14
+        ! running sums, without hnumo_sync.  coriolis_df: c_loc of coriolis_df(npoin) or c_null_ptr
+        ! (f = 0); zref: c_loc of zref(npoin,nlayers) or c_null_ptr (0).  every = k >= 1: the engine
+        ! samples after every k-th successful hnumo_ti_rk_bcl itself.
+        integer(c_int) function hnumo_cov_begin(eng, coriolis_df, zref, every) bind(C, name='hnumo_cov_begin')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng, coriolis_df, zref
+            integer(c_int32_t), value :: every
+        end function hnumo_cov_begin
+
+        integer(c_int) function hnumo_cov_accumulate(eng) bind(C, name='hnumo_cov_accumulate')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_cov_accumulate
+
+        ! out(14,npoin,nlayers) = S_h, S_u, S_v, S_uh, S_vh, S_uuh, S_uvh, S_vvh, S_d, S_dd, S_a, S_ua,
+        ! S_va, S_qa; n = 14*npoin*nlayers
+        integer(c_int) function hnumo_cov_sums(eng, out, n, nsamples) bind(C, name='hnumo_cov_sums')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: nsamples
+        end function hnumo_cov_sums
+
+        integer(c_int) function hnumo_cov_set_sums(eng, sums, n, nsamples) bind(C, name='hnumo_cov_set_sums')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: sums(*)
+            integer(c_int64_t), value :: n, nsamples
+        end function hnumo_cov_set_sums
+
+        ! out(16,npoin,nlayers) = hbar, ubar, vbar, um, vm, Ruu, Ruv, Rvv, Fu, Fv, dbar, dvar, qm, Qu, Qv,
+        ! ens; n = 16*npoin*nlayers
+        integer(c_int) function hnumo_cov_fields(eng, out, n) bind(C, name='hnumo_cov_fields')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_cov_fields
+
+        ! out(3,nlayers) = the integrals of hbar*(0.5*(Ruu+Rvv)), dvar, hbar*ens; n = 3*nlayers
+        integer(c_int) function hnumo_cov_integrals(eng, out, n) bind(C, name='hnumo_cov_integrals')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_cov_integrals
+
+        integer(c_int) function hnumo_cov_end(eng) bind(C, name='hnumo_cov_end')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_cov_end
+
         ! Sample sets (see include/hnumo_engine.h): the device state, or the flow statistics, at
         ! arbitrary points by the element's own Lagrange interpolant -- an output grid, a
         ! cross-section, stations -- on demand or after every k-th step into a series on the device.
@@ -394,7 +451,7 @@ module hnumo_engine_c
         end function hnumo_sample_plan
 
         ! out(V,M), n = V*M; V = 5*nlayers + 4 (HNUMO_SAMPLE_STATE), 5*nlayers (HNUMO_SAMPLE_STATS) or
-        ! 4*nlayers (HNUMO_SAMPLE_VORT)
+        ! 4*nlayers (HNUMO_SAMPLE_VORT) or 16*nlayers (HNUMO_SAMPLE_COV)
         integer(c_int) function hnumo_sample(eng, id, out, n) bind(C, name='hnumo_sample')
             import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
             type(c_ptr), value :: eng

@@ -344,6 +344,72 @@ int hnumo_vort_record(hnumo_engine *eng);
 int hnumo_vort_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear);
 int hnumo_vort_end(hnumo_engine *eng);
 
+/* Eddy covariances on the device state (additive in ABI v10): the thickness-weighted Reynolds stress
+ * tensor (the EKE is half its trace), the eddy thickness flux (bolus transport), the interface and SSH
+ * variance, the eddy potential-vorticity flux and the eddy potential enstrophy -- covariances of fields
+ * that decorrelate within a few steps, so they are accumulated from every step where the state lives;
+ * the PV terms need the gradient of every sampled state.  Definitions (normative; no FMA, IEEE
+ * division, every sum left to right).  Per owned node I of element e and layer k, per sample:
+ *   dp, h, u, v        as hnumo_stats / hnumo_vort form them (h = (alpha_k/gravity)*dp, quotient first;
+ *                      u = q2/dp; v = q3/dp)
+ *   z                  = elevation of layer k's top interface as hnumo_layer_fields forms it (row 5;
+ *                        summed upward from zbot_df)
+ *   d                  = z - zref(I,k)                  (zref given at begin, NULL: 0.0)
+ *   zeta, pv           = zeta and pv of hnumo_vort for this node and layer (f as given at begin, NULL: 0.0)
+ *   a                  = zeta + f(I)
+ * One SAMPLE adds these 14 terms to running sums (plain adds in sample order from +0.0; one lane owns a
+ * node's sums):
+ *   S_h  += h        S_u  += u          S_v  += v
+ *   S_uh += u*h      S_vh += v*h
+ *   S_uuh += (u*u)*h S_uvh += (u*v)*h   S_vvh += (v*v)*h
+ *   S_d  += d        S_dd += d*d
+ *   S_a  += a        S_ua += u*a        S_va += v*a        S_qa += pv*a
+ * zref exists because the top interface of an interior layer sits near -1500 m while its variance is a
+ * few m^2: without the shift S_dd/n - dbar^2 loses eight digits.  Pass the rest elevations, or on a
+ * restart the zref of the first run.  The fields, 16 per node and layer, after n samples, N = double(n):
+ *   hbar = S_h/N   ubar = S_u/N   vbar = S_v/N   um = S_uh/S_h   vm = S_vh/S_h
+ *   Ruu = S_uuh/S_h - um*um    Ruv = S_uvh/S_h - um*vm    Rvv = S_vvh/S_h - vm*vm
+ *   Fu  = S_uh/N - ubar*hbar   Fv  = S_vh/N - vbar*hbar
+ *   dbar = S_d/N               dvar = S_dd/N - dbar*dbar
+ *   qm  = S_a/S_h              Qu  = S_ua/S_h - um*qm     Qv = S_va/S_h - vm*qm
+ *   ens = 0.5*(S_qa/S_h - qm*qm)
+ * Ruu, Ruv, Rvv: the thickness-weighted Reynolds stresses; Fu, Fv: the eddy thickness flux (Fu/hbar is
+ * the bolus velocity); dvar of layer 1: the SSH variance; Qu, Qv: the thickness-weighted eddy PV flux
+ * (h*pv = a); ens: the eddy potential enstrophy.  Integrals, per layer, over the rank's owned elements:
+ * of hbar*(0.5*(Ruu+Rvv)), of dvar and of hbar*ens, summed exactly as the flow statistics' series (per
+ * element the products jac_I * x_I added in node order from the first, the element sums by the pairwise
+ * tree over the element positions; the host adds the ranks).  No series, no floating-point atomics.
+ * Every value has the bits of the numpy mirror hnumo/covariance.py (HostEddyCov) on the synced states.
+ * Nodes of ghost elements are never accumulated and read 0 everywhere.  DESIGN.md §6.1.7.
+ *
+ * hnumo_cov_begin: coriolis_df(npoin) or NULL: f = 0; zref(npoin,nlayers) or NULL: 0.  every = 0: only
+ *   hnumo_cov_accumulate takes samples; every = k >= 1: the engine also takes one after every k-th
+ *   successful hnumo_ti_rk_bcl (hnumo_group_ti_rk_bcl for grouped engines) since begin, once the step's
+ *   abort / retry handling has finished, after the flow statistics' and the vorticity's sample and before
+ *   the sample sets (a COV set sees the new sums) and the floats; a step that returns non-zero is not
+ *   sampled.  A second call resets.  nlayers must be 2 or 3 and ngl 3, 4, 5, 6 or 8.  Independent of
+ *   hnumo_stats_* and hnumo_vort_*: neither needs to be on.
+ * hnumo_cov_accumulate: one sample of the state on the device, ordered after the step on the engine's
+ *   stream, outside the captured step, nothing copied back: the step's launches, graph and bits are the
+ *   same with covariances on or off.
+ * hnumo_cov_sums / hnumo_cov_set_sums: out / in (14,npoin,nlayers) = S_h, S_u, S_v, S_uh, S_vh, S_uuh,
+ *   S_uvh, S_vvh, S_d, S_dd, S_a, S_ua, S_va, S_qa in the index order of hnumo_layer_fields,
+ *   n = 14*npoin*nlayers, and the sample count: a restarted run restores them and goes on.
+ * hnumo_cov_fields: out(16,npoin,nlayers) = hbar, ubar, vbar, um, vm, Ruu, Ruv, Rvv, Fu, Fv, dbar, dvar,
+ *   qm, Qu, Qv, ens; n = 16*npoin*nlayers.
+ * hnumo_cov_integrals: out(3,nlayers), n = 3*nlayers.
+ * hnumo_cov_end: frees the buffers; a no-op before hnumo_cov_begin.
+ * All return 4, with a message in hnumo_last_error, before hnumo_cov_begin, for a wrong n or a negative
+ * every; a sample returns 4 before any state was uploaded; hnumo_cov_fields and hnumo_cov_integrals
+ * return 4 with no samples.                                                                       */
+int hnumo_cov_begin(hnumo_engine *eng, const double *coriolis_df, const double *zref, int32_t every);
+int hnumo_cov_accumulate(hnumo_engine *eng);
+int hnumo_cov_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples);
+int hnumo_cov_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples);
+int hnumo_cov_fields(hnumo_engine *eng, double *out, int64_t n);
+int hnumo_cov_integrals(hnumo_engine *eng, double *out, int64_t n);
+int hnumo_cov_end(hnumo_engine *eng);
+
 /* Sample sets (additive in ABI v10): the state on the device, or the accumulated flow statistics,
  * evaluated at arbitrary points -- a regular output grid, a cross-section, a few stations -- by the
  * element's own Lagrange interpolant, where the post-processing scripts griddata the synced nodal
@@ -361,6 +427,8 @@ int hnumo_vort_end(hnumo_engine *eng);
  *   HNUMO_SAMPLE_STATS  V = 5*nlayers: hbar, um, vm, mke, eke of hnumo_stats_fields per layer
  *   HNUMO_SAMPLE_VORT   V = 4*nlayers: zeta, delta, pv, ow of hnumo_vort_fields per layer, formed from
  *                       the set's own elements (f as hnumo_vort_begin took it)
+ *   HNUMO_SAMPLE_COV    V = 16*nlayers: the 16 fields of hnumo_cov_fields per layer, interpolated as
+ *                       the STATS source is
  * Value: val = sum_j Ly[j] * r_j with r_j = sum_i Lx[i] * F(e, j*ngl + i), both sums left to right
  * from their first product (no FMA).  Points with elem = 0 read 0.0 in every row.  At xi = xgl[a],
  * eta = xgl[b] the weights are exactly 0 and 1: the sample is the nodal value.  Every value has the
@@ -392,10 +460,12 @@ int hnumo_vort_end(hnumo_engine *eng);
  * hnumo_last_error, for an unknown id, a wrong n or M, negative arguments, invalid points or
  * geometry, a ninth set; a sample returns 4 before any state was uploaded, when the series is full
  * or absent, for a STATS set before hnumo_stats_begin or with no statistics samples, and for a VORT
- * set before hnumo_vort_begin or after hnumo_vort_end (the set needs f: creating it is refused too). */
+ * set before hnumo_vort_begin or after hnumo_vort_end (the set needs f: creating it is refused too);
+ * for a COV set before hnumo_cov_begin (creating it is refused too) or with no covariance samples. */
 #define HNUMO_SAMPLE_STATE 0
 #define HNUMO_SAMPLE_STATS 1
 #define HNUMO_SAMPLE_VORT 2
+#define HNUMO_SAMPLE_COV 3
 int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
                         int64_t M, int32_t source, int32_t *id);
 int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, const int32_t *elem, const double *xi_eta, int64_t M,
