@@ -6,9 +6,10 @@
 // ~20 baroclinic kernels) is captured once into a hipGraph and replayed.  The run diagnostics of
 // the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) and the
 // online flow statistics (kernels_stats.hip: hnumo_stats_*), the vorticity products (kernels_vort.hip:
-// hnumo_vort_*), the eddy covariances (kernels_cov.hip: hnumo_cov_*), the sample sets
-// (kernels_sample.hip) and the float sets (kernels_float.hip: hnumo_floats_*) are plain launches on the
-// same stream between replays; the host side of those five observers is observers.hip, included below.
+// hnumo_vort_*), the eddy covariances (kernels_cov.hip: hnumo_cov_*), the energy budget
+// (kernels_energy.hip: hnumo_energy_*), the sample sets (kernels_sample.hip) and the float sets
+// (kernels_float.hip: hnumo_floats_*) are plain launches on the same stream between replays; the host
+// side of those six observers is observers.hip, included below.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -37,6 +38,7 @@
 #include "kernels_stats.hip"
 #include "kernels_vort.hip"
 #include "kernels_cov.hip"
+#include "kernels_energy.hip"
 #include "kernels_sample.hip"
 #include "kernels_float.hip"
 #include "kernels_wind.hip"
@@ -238,6 +240,17 @@ struct hnumo_engine {
     int every = 0;
     TreeSum tree;
   } cov;
+  // energy budget (hnumo_energy_begin .. hnumo_energy_end; kernels_energy.hip): the caller's zref (NULL:
+  // 0), the running sums (S_W, S_D) [npoin_q] pairs and S_V [L][npoin], the samples taken, the element
+  // partials [3L+2][ne] with their tree and the series [capacity][3L+2] (capacity 0: `every` stands alone
+  // and counts in series.steps all the same)
+  struct Energy {
+    bool on = false;
+    double *zref = nullptr, *sq = nullptr, *sv = nullptr;
+    int64_t nsamples = 0;
+    TreeSum tree;
+    Series series;
+  } energy;
   // sample sets (hnumo_sample_*): the host plan (sample_plan.h), its tables on the device, one
   // sample's output [V][M]
   struct SampleSet {
@@ -1622,6 +1635,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   stats_free(eng);
   vort_free(eng);
   cov_free(eng);
+  energy_free(eng);
   for (int id = 0; id < SP_MAXSETS; id++) sample_free(eng, id);
   for (int id = 0; id < FL_MAXSETS; id++) floats_free(eng, id);
   wind_free(eng);

@@ -40,14 +40,13 @@ struct VortArgs {
   int npoin, ne;         // ne: the owned elements
 };
 
-// The statements above for node (i, j) of one element.  su, sv: the element's u, v tiles in LDS
-// (node (i, j) at [j*NGL + i]); Di[m] = D(m,i), Dj[m] = D(m,j); ex..ny = ksi_x, ksi_y, eta_x, eta_y.
-// o = zeta, delta, pv, ow.  The one text of the arithmetic: vort_kernel and sample_kernel's VORT
-// source both call it.
+// The element's own gradient at node (i, j).  su, sv: the element's u, v tiles in LDS (node (i, j) at
+// [j*NGL + i]); Di[m] = D(m,i), Dj[m] = D(m,j); ex..ny = ksi_x, ksi_y, eta_x, eta_y.  The one text of the
+// gradient: vort_node below and energy_sample_kernel (kernels_energy.hip) call it.
 template <int NGL>
-__device__ __forceinline__ void vort_node(const double *su, const double *sv, int i, int j, const double (&Di)[NGL],
-                                          const double (&Dj)[NGL], double ex, double ey, double nx, double ny, double f,
-                                          double h, double (&o)[4]) {
+__device__ __forceinline__ void vort_grad(const double *su, const double *sv, int i, int j, const double (&Di)[NGL],
+                                          const double (&Dj)[NGL], double ex, double ey, double nx, double ny, double &u_x,
+                                          double &u_y, double &v_x, double &v_y) {
   const double *ur = su + j * NGL, *vr = sv + j * NGL, *uc = su + i, *vc = sv + i;
   double u_xi = Di[0] * ur[0], u_eta = Dj[0] * uc[0], v_xi = Di[0] * vr[0], v_eta = Dj[0] * vc[0];
 #pragma unroll
@@ -57,8 +56,18 @@ __device__ __forceinline__ void vort_node(const double *su, const double *sv, in
     v_xi = v_xi + Di[m] * vr[m];
     v_eta = v_eta + Dj[m] * vc[m * NGL];
   }
-  const double u_x = u_xi * ex + u_eta * nx, u_y = u_xi * ey + u_eta * ny;
-  const double v_x = v_xi * ex + v_eta * nx, v_y = v_xi * ey + v_eta * ny;
+  u_x = u_xi * ex + u_eta * nx, u_y = u_xi * ey + u_eta * ny;
+  v_x = v_xi * ex + v_eta * nx, v_y = v_xi * ey + v_eta * ny;
+}
+
+// The statements above for node (i, j) of one element (arguments as vort_grad's).  o = zeta, delta, pv, ow.
+// The one text of the arithmetic: vort_kernel and sample_kernel's VORT source both call it.
+template <int NGL>
+__device__ __forceinline__ void vort_node(const double *su, const double *sv, int i, int j, const double (&Di)[NGL],
+                                          const double (&Dj)[NGL], double ex, double ey, double nx, double ny, double f,
+                                          double h, double (&o)[4]) {
+  double u_x, u_y, v_x, v_y;
+  vort_grad<NGL>(su, sv, i, j, Di, Dj, ex, ey, nx, ny, u_x, u_y, v_x, v_y);
   const double zeta = v_x - u_y;
   const double sn = u_x - v_y, ss = v_x + u_y;
   o[0] = zeta;

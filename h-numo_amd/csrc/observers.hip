@@ -1,14 +1,14 @@
 // observers.hip -- what runs after a successful step of the resident state: the online flow
 // statistics (kernels_stats.hip), the vorticity products (kernels_vort.hip), the eddy covariances
-// (kernels_cov.hip), the sample sets (kernels_sample.hip, sample_plan.h) and the float sets
-// (kernels_float.hip, float_plan.h).
+// (kernels_cov.hip), the energy budget (kernels_energy.hip, energy_plan.h), the sample sets
+// (kernels_sample.hip, sample_plan.h) and the float sets (kernels_float.hip, float_plan.h).
 //
 // Part of engine.hip's translation unit: included there once fail, HIPCHK and struct hnumo_engine
 // (with Series and TreeSum) are defined.  All of it is plain launches on the engine stream outside
 // the captured step: the step's launches, graph and bits are the same with or without observers.
 //
 // An observer is a kernel, a Series, an entry in observers_after_step and a free in
-// hnumo_engine_destroy; the pieces below are what the five have in common (the eddy covariances keep
+// hnumo_engine_destroy; the pieces below are what the six have in common (the eddy covariances keep
 // no series: their `every` stands alone).
 
 // ------------------------------------------------------------------ shared pieces
@@ -638,6 +638,189 @@ extern "C" int hnumo_cov_integrals(hnumo_engine *eng, double *out, int64_t n) {
   tree_sum(eng, eng->cov.tree, rows, ne, eng->cov.integ);
   HIPCHK(hipGetLastError());
   return download(eng, out, eng->cov.integ, (size_t)rows * sizeof(double));
+}
+
+// ------------------------------------------------------------------ energy budget
+// eng->energy: the caller's zref (NULL: 0), the running sums (S_W, S_D) [npoin_q] pairs and S_V
+// [L][npoin], the element partials [3L+2][ne] and their tree, the series [capacity][3L+2]; nsamples:
+// samples taken since begin
+static void energy_free(hnumo_engine *eng) {
+  auto &en = eng->energy;
+  dfree(en.zref, en.sq, en.sv);
+  tree_free(en.tree);
+  series_free(en.series);
+  en.on = false;
+  en.nsamples = 0;
+}
+
+static size_t energy_nquad(const hnumo_engine *eng) { return 2 * (size_t)eng->npq; }
+static size_t energy_nnodal(const hnumo_engine *eng) { return (size_t)eng->npoin * eng->L; }
+
+extern "C" int hnumo_energy_begin(hnumo_engine *eng, const double *zref, int32_t every, int32_t series_capacity) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (every < 0 || series_capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_begin: every and series_capacity must be >= 0, got " +
+                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl) || eng->nq != 2 * eng->ngl - 1)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_begin: unsupported nlayers or ngl (nlayers 1..3; ngl 3, 4, 5, 6 or 8), got " +
+                                            std::to_string(eng->L) + ", " + std::to_string(eng->ngl));
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
+  energy_free(eng);
+  auto &en = eng->energy;
+  const int rows = en_rows(eng->L);
+  bool ok = alloc_doubles(&en.sq, energy_nquad(eng)) && alloc_doubles(&en.sv, energy_nnodal(eng)) &&
+            (series_capacity == 0 || tree_alloc(en.tree, rows, eng->nelem_owned)) &&
+            (!zref || alloc_doubles(&en.zref, energy_nnodal(eng))) &&
+            series_begin(eng, en.series, rows, every, series_capacity, true) == hipSuccess;
+  if (ok && zref) ok = hipMemcpy(en.zref, zref, energy_nnodal(eng) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    energy_free(eng);
+    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_energy_begin: device allocation or upload failed");
+  }
+  // (the points of ghost elements are never visited: their sums stay +0.0)
+  HIPCHK(hipMemsetAsync(en.sq, 0, energy_nquad(eng) * sizeof(double), eng->stream));
+  HIPCHK(hipMemsetAsync(en.sv, 0, energy_nnodal(eng) * sizeof(double), eng->stream));
+  en.on = true;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_energy_end(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->energy.on) return HNUMO_OK;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  energy_free(eng);
+  return HNUMO_OK;
+}
+
+template <int NGL, int L, bool SERIES>
+static void energy_launch(int botfr, int nb, hipStream_t st, const EnergyArgs &a) {
+  switch (botfr) {
+    case 0: hipLaunchKernelGGL((energy_sample_kernel<NGL, L, 0, SERIES>), dim3(nb), dim3(EN_BS), 0, st, a); break;
+    case 1: hipLaunchKernelGGL((energy_sample_kernel<NGL, L, 1, SERIES>), dim3(nb), dim3(EN_BS), 0, st, a); break;
+    default: hipLaunchKernelGGL((energy_sample_kernel<NGL, L, 2, SERIES>), dim3(nb), dim3(EN_BS), 0, st, a); break;
+  }
+}
+
+// one sample of the state and the wind on the device, ordered after what is on the engine stream; no
+// copy back
+static int energy_sample(hnumo_engine *eng, const char *who) {
+  auto &en = eng->energy;
+  if (!en.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_energy_begin first");
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (eng->p.botfr < 0 || eng->p.botfr > 2)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": botfr must be 0, 1 or 2, got " + std::to_string(eng->p.botfr));
+  const bool series = en.series.cap > 0;
+  if (series)
+    if (int rc = series_full(eng, en.series, who, "the series", "samples", "accumulated")) return rc;
+  const int ne = eng->nelem_owned, EPG = en_epg(eng->ngl);
+  if (ne > 0) {
+    EnergyArgs a{};
+    a.q = eng->q;
+    a.alpha = eng->alpha;
+    a.nstat = eng->nstat;
+    a.qstat = eng->qstat;
+    a.zref = en.zref;
+    a.psiq = eng->basis;
+    a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
+    a.sq = (double2 *)en.sq;
+    a.sv = en.sv;
+    a.part = en.tree.part;
+    a.gravity = eng->p.gravity;
+    a.cd = eng->p.cd_mlswe;
+    a.visc = eng->p.visc_mlswe;
+    a.npoin = eng->npoin;
+    a.npq = eng->npq;
+    a.ne = ne;
+    const int nb = std::max(1, std::min((ne + EPG - 1) / EPG, 8192));
+    with_ngl(eng->ngl, [&](auto ngl) {
+      with_L(eng->L, [&](auto l) {
+        constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
+        if (series)
+          energy_launch<NGL, L, true>(eng->p.botfr, nb, eng->stream, a);
+        else
+          energy_launch<NGL, L, false>(eng->p.botfr, nb, eng->stream, a);
+      });
+    });
+    if (series) tree_sum(eng, en.tree, en_rows(eng->L), ne, series_slot(en.series));
+    HIPCHK(hipGetLastError());
+  }
+  if (series) en.series.count++;
+  en.nsamples++;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_energy_sample(hnumo_engine *eng) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return energy_sample(eng, "hnumo_energy_sample");
+}
+
+extern "C" int hnumo_energy_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_series: call hnumo_energy_begin first");
+  if (eng->energy.series.cap == 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_series: no series (hnumo_energy_begin was given series_capacity = 0)");
+  return series_read(eng, eng->energy.series, 0, 0, out, n, count, clear, "hnumo_energy_series", "(3*nlayers+2)");
+}
+
+// 0, or the refusal of a wrong nq2 or nn
+static int energy_sizes(hnumo_engine *eng, const char *who, int64_t nq2, int64_t nn) {
+  const int64_t wq = (int64_t)energy_nquad(eng), wn = (int64_t)energy_nnodal(eng);
+  if (nq2 != wq)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": nq2 must be 2*npoin_q = " + std::to_string(wq) + ", got " +
+                                            std::to_string(nq2));
+  if (nn != wn)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": nn must be npoin*nlayers = " + std::to_string(wn) + ", got " +
+                                            std::to_string(nn));
+  return 0;
+}
+
+// (the device layouts are the caller's: (2,npoin_q) and (npoin,nlayers))
+extern "C" int hnumo_energy_sums(hnumo_engine *eng, double *quad2, int64_t nq2, double *nodal, int64_t nn, int64_t *nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_sums: call hnumo_energy_begin first");
+  if (!quad2 || !nodal) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_sums: quad2 or nodal is NULL");
+  if (int rc = energy_sizes(eng, "hnumo_energy_sums", nq2, nn)) return rc;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipMemcpyAsync(quad2, eng->energy.sq, (size_t)nq2 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  if (int rc = download(eng, nodal, eng->energy.sv, (size_t)nn * sizeof(double))) return rc;
+  if (nsamples) *nsamples = eng->energy.nsamples;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_energy_set_sums(hnumo_engine *eng, const double *quad2, int64_t nq2, const double *nodal, int64_t nn,
+                                     int64_t nsamples) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_set_sums: call hnumo_energy_begin first");
+  if (!quad2 || !nodal) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_set_sums: quad2 or nodal is NULL");
+  if (int rc = energy_sizes(eng, "hnumo_energy_set_sums", nq2, nn)) return rc;
+  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_set_sums: nsamples must be >= 0");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipMemcpyAsync(eng->energy.sq, quad2, (size_t)nq2 * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HIPCHK(hipMemcpyAsync(eng->energy.sv, nodal, (size_t)nn * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  eng->energy.nsamples = nsamples;
+  return HNUMO_OK;
+}
+
+// the sums divided by double(nsamples), on the host: S_W/N, S_D/N (2,npoin_q) and S_V/N (npoin,nlayers)
+extern "C" int hnumo_energy_means(hnumo_engine *eng, double *quad2, int64_t nq2, double *nodal, int64_t nn) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_means: call hnumo_energy_begin first");
+  if (!quad2 || !nodal) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_means: quad2 or nodal is NULL");
+  if (int rc = energy_sizes(eng, "hnumo_energy_means", nq2, nn)) return rc;
+  if (eng->energy.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_means: no samples yet");
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipMemcpyAsync(quad2, eng->energy.sq, (size_t)nq2 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+  if (int rc = download(eng, nodal, eng->energy.sv, (size_t)nn * sizeof(double))) return rc;
+  const double N = (double)eng->energy.nsamples;
+  for (int64_t x = 0; x < nq2; x++) quad2[x] = quad2[x] / N;
+  for (int64_t x = 0; x < nn; x++) nodal[x] = nodal[x] / N;
+  return HNUMO_OK;
 }
 
 // ------------------------------------------------------------------ sample sets
@@ -1535,7 +1718,7 @@ extern "C" int hnumo_floats_settle(hnumo_engine *eng, int32_t id) {
 // ------------------------------------------------------------------ after a successful step
 // Called once run_steps has returned 0 (so a step redone on per-stage launches is observed once), in
 // this order: the statistics' sample; the vorticity series' sample; the eddy covariances' sample; the
-// sample sets' recordings, which see the new sums of a set on the statistics or the covariances; the
+// energy budget's sample; the sample sets' recordings, which see the new sums of a set on the statistics or the covariances; the
 // float sets' advance by params.dt, last.  Every
 // observer runs whatever the others return (a float cannot skip a step because a series was full);
 // the first non-zero code is returned.
@@ -1550,6 +1733,8 @@ static int observers_after_step(hnumo_engine *eng) {
     run(vort_form(eng, true, "vorticity series after the step (the step itself succeeded)"));
   if (eng->cov.on && eng->cov.every > 0 && ++eng->cov.steps % eng->cov.every == 0)
     run(cov_sample(eng, "eddy covariances after the step (the step itself succeeded)"));
+  if (eng->energy.on && series_due(eng->energy.series))
+    run(energy_sample(eng, "energy budget after the step (the step itself succeeded)"));
   for (int id = 0; id < SP_MAXSETS; id++) {
     auto &s = eng->samples[id];
     if (s.used && series_due(s.series)) run(sample_record(eng, s, id, "sample series after the step (the step itself succeeded)"));

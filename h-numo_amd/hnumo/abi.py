@@ -125,6 +125,18 @@ def declare_cov(L):
     L.hnumo_cov_end.argtypes = [vp]
 
 
+def declare_energy(L):
+    """The energy budget's calls of the loaded library L (hnumo_energy_*)."""
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.hnumo_energy_begin.argtypes = [vp, _dp, i32, i32]
+    L.hnumo_energy_sample.argtypes = [vp]
+    L.hnumo_energy_series.argtypes = [vp, _dp, i64, C.POINTER(i64), i32]
+    L.hnumo_energy_sums.argtypes = [vp, _dp, i64, _dp, i64, C.POINTER(i64)]
+    L.hnumo_energy_set_sums.argtypes = [vp, _dp, i64, _dp, i64, i64]
+    L.hnumo_energy_means.argtypes = [vp, _dp, i64, _dp, i64]
+    L.hnumo_energy_end.argtypes = [vp]
+
+
 def ptr(a: np.ndarray | None):
     """Pointer to a contiguous Fortran-order array (keeps no reference: caller owns it)."""
     if a is None:

@@ -282,7 +282,7 @@ def restart_state(case, path):
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
               time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1, floats=None,
-              vorticity=None, vort_every=1, wind=None, eddy_cov=None, cov_every=1):
+              vorticity=None, vort_every=1, wind=None, eddy_cov=None, cov_every=1, energy=None, energy_every=1):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
@@ -322,7 +322,15 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     cov_every-th step of this loop (after flow_stats' and the vorticity's sample, before the floats) it
     gets add(q).  The device object (begun with every = 0) samples the engine's state where it lives (q
     is ignored, no sync); the host object reads the host arrays, which a resident stepper syncs for it
-    first.  None: nothing changes."""
+    first.  None: nothing changes.
+
+    energy: a hnumo.energy.DeviceEnergy or HostEnergy, handled as eddy_cov is: after every energy_every-th
+    step of this loop (after eddy_cov's sample, before the floats) it gets add(q, tau).  The device object
+    (begun with every = 0) samples the state and the wind where they live (no sync); the host object reads
+    the host arrays and is given the wind that `wind` blended for that step (wind.tau; None without `wind`:
+    the case's own tau_wind).  None: nothing changes."""
+    if energy is not None and int(energy_every) < 1:
+        raise ValueError("energy_every must be >= 1")
     if eddy_cov is not None and int(cov_every) < 1:
         raise ValueError("cov_every must be >= 1")
     if vorticity is not None and int(vort_every) < 1:
@@ -402,6 +410,11 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
             if resident and getattr(eddy_cov, "needs_host_state", True):
                 stepper.sync(q, qb, qp)
             eddy_cov.add(q)
+        if energy is not None and nstep % int(energy_every) == 0:
+            on_host = getattr(energy, "needs_host_state", True)
+            if resident and on_host:
+                stepper.sync(q, qb, qp)
+            energy.add(q, wind.tau if on_host and wind is not None else None)
         for fs in float_sets:
             if resident and getattr(fs, "needs_host_state", True):
                 stepper.sync(q, qb, qp)

@@ -110,6 +110,7 @@ def lib():
         L.hnumo_group_floats_advance.argtypes = [C.POINTER(vp), C.c_int, i32, C.c_double]
         abi.declare_float_sensors(L)
         abi.declare_cov(L)
+        abi.declare_energy(L)
         L.hnumo_wind_begin.argtypes = [vp, dp, i64, i32]
         L.hnumo_wind_set.argtypes = [vp, dp, i32]
         L.hnumo_wind_schedule.argtypes = [vp, dp, i32, i32, i32, i32]
@@ -486,6 +487,55 @@ class Engine:
 
     def cov_end(self):
         self._check(lib().hnumo_cov_end(self.h))
+
+    # ---- energy budget of the device state (hnumo_energy_*; mirror: hnumo/energy.py)
+    def energy_begin(self, zref=None, every: int = 0, series: int = 0):
+        """Allocate and zero the running sums (again: reset).  zref (npoin, nlayers), or None: 0.  every =
+        k >= 1: the engine samples itself after every k-th successful step; series: samples the series of
+        3*nlayers + 2 integrals can hold (0: none)."""
+        npoin, L = self.dims["npoin"], self.dims["nlayers"]
+        zp = None
+        if zref is not None:
+            z = np.array(zref, dtype=np.float64, order="F")
+            if z.shape != (npoin, L):
+                raise ValueError(f"zref: shape {z.shape}, expected (npoin, nlayers) = ({npoin}, {L})")
+            zp = z.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(lib().hnumo_energy_begin(self.h, zp, int(every), int(series)))
+
+    def energy_sample(self):
+        """One sample of the state and the wind on the device; nothing is copied back."""
+        self._check(lib().hnumo_energy_sample(self.h))
+
+    def energy_series(self, clear: bool = False):
+        """(3*nlayers + 2, count) = KE_1..L, APE_1..L, V_1..L, W, D per sample; clear empties the series."""
+        return self._series(lib().hnumo_energy_series, (3 * self.dims["nlayers"] + 2,), clear=clear)
+
+    def _energy_out(self):
+        return (np.zeros((2, self.dims["npoin_q"]), order="F"), np.zeros((self.dims["npoin"], self.dims["nlayers"]), order="F"))
+
+    def energy_sums(self):
+        """(quad (2, npoin_q) = S_W, S_D; nodal (npoin, nlayers) = S_V; the sample count)."""
+        quad, nodal = self._energy_out()
+        n = C.c_int64()
+        self._check(lib().hnumo_energy_sums(self.h, _dp(quad), quad.size, _dp(nodal), nodal.size, C.byref(n)))
+        return quad, nodal, n.value
+
+    def energy_set_sums(self, quad, nodal, nsamples: int):
+        """Restore the sums and a sample count, e.g. of a run being restarted."""
+        a, b = np.array(quad, dtype=np.float64, order="F"), np.array(nodal, dtype=np.float64, order="F")
+        d = self.dims
+        self._check(lib().hnumo_energy_set_sums(self.h, _dp(a, 2 * d["npoin_q"], "quad"), a.size,
+                                                _dp(b, d["npoin"] * d["nlayers"], "nodal"), b.size, int(nsamples)))
+
+    def energy_means(self):
+        """(quad (2, npoin_q) = S_W/N, S_D/N; nodal (npoin, nlayers) = S_V/N): the maps of mean wind power
+        input, drag and dissipation."""
+        quad, nodal = self._energy_out()
+        self._check(lib().hnumo_energy_means(self.h, _dp(quad), quad.size, _dp(nodal), nodal.size))
+        return quad, nodal
+
+    def energy_end(self):
+        self._check(lib().hnumo_energy_end(self.h))
 
     # ---- sample sets on the device state (hnumo_sample_*; mirror and helpers: hnumo/sample.py)
     def _sample_nval(self, source: int) -> int:

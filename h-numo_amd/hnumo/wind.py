@@ -124,6 +124,8 @@ class DeviceWind:
     def tau_wind(self):
         return self.engine.wind_get()[0]
 
+    tau = tau_wind                 # (the wind the last step used, under the name HostWind keeps it)
+
     def end(self):
         self.engine.wind_end()
         self._installed = False
@@ -138,9 +140,11 @@ class HostWind:
         self.coef = _table(coef, self.patterns.shape[2])
         self.mode = _mode(mode)
         self._row = -1
+        self.tau = None            # the wind handed over last (None: none yet)
 
     def before_step(self, stepper, nstep: int):
         r = row_for(int(nstep), self.coef.shape[1], 0, self.mode)
         if r >= 0 and r != self._row:
-            stepper.set_tau_wind(blend(self.patterns, self.coef[:, r]))
+            self.tau = blend(self.patterns, self.coef[:, r])
+            stepper.set_tau_wind(self.tau)
             self._row = r

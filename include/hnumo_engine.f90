@@ -90,6 +90,8 @@ module hnumo_engine_c
         hnumo_vort_begin, hnumo_vort_fields, hnumo_vort_record, hnumo_vort_series, hnumo_vort_end, &
         hnumo_cov_begin, hnumo_cov_accumulate, hnumo_cov_sums, hnumo_cov_set_sums, hnumo_cov_fields, &
         hnumo_cov_integrals, hnumo_cov_end, &
+        hnumo_energy_begin, hnumo_energy_sample, hnumo_energy_series, hnumo_energy_sums, hnumo_energy_set_sums, &
+        hnumo_energy_means, hnumo_energy_end, &
         hnumo_sample_create, hnumo_sample_create_ref, hnumo_sample_plan, hnumo_sample, &
         hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy, &
         hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
@@ -414,6 +416,63 @@ module hnumo_engine_c
             import :: c_int, c_ptr
             type(c_ptr), value :: eng
         end function hnumo_cov_end
+
+        ! Energy budget on the device state (see include/hnumo_engine.h): wind work and bottom drag at the
+        ! quadrature points, interior viscous dissipation at the nodes, with the series of KE, APE, V per
+        ! layer and W, D, without hnumo_sync.  zref: c_loc of zref(npoin,nlayers) or c_null_ptr (0).
+        ! every = k >= 1: the engine samples after every k-th successful hnumo_ti_rk_bcl itself;
+        ! series_capacity: samples the series can hold (0: sums only).
+        integer(c_int) function hnumo_energy_begin(eng, zref, every, series_capacity) bind(C, name='hnumo_energy_begin')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng, zref
+            integer(c_int32_t), value :: every, series_capacity
+        end function hnumo_energy_begin
+
+        integer(c_int) function hnumo_energy_sample(eng) bind(C, name='hnumo_energy_sample')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_energy_sample
+
+        ! out(3*nlayers+2, count) = KE_1..L, APE_1..L, V_1..L, W, D per sample; out: c_loc of the array, or
+        ! c_null_ptr for the count alone
+        integer(c_int) function hnumo_energy_series(eng, out, n, count, clear) bind(C, name='hnumo_energy_series')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr
+            type(c_ptr), value :: eng, out
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: count
+            integer(c_int32_t), value :: clear
+        end function hnumo_energy_series
+
+        ! quad2(2,npoin_q) = S_W, S_D, nq2 = 2*npoin_q; nodal(npoin,nlayers) = S_V, nn = npoin*nlayers
+        integer(c_int) function hnumo_energy_sums(eng, quad2, nq2, nodal, nn, nsamples) bind(C, name='hnumo_energy_sums')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: quad2(*), nodal(*)
+            integer(c_int64_t), value :: nq2, nn
+            integer(c_int64_t), intent(out) :: nsamples
+        end function hnumo_energy_sums
+
+        integer(c_int) function hnumo_energy_set_sums(eng, quad2, nq2, nodal, nn, nsamples) &
+                bind(C, name='hnumo_energy_set_sums')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(in) :: quad2(*), nodal(*)
+            integer(c_int64_t), value :: nq2, nn, nsamples
+        end function hnumo_energy_set_sums
+
+        ! quad2(2,npoin_q) = S_W/N, S_D/N; nodal(npoin,nlayers) = S_V/N: the maps of mean wind power input,
+        ! drag and dissipation
+        integer(c_int) function hnumo_energy_means(eng, quad2, nq2, nodal, nn) bind(C, name='hnumo_energy_means')
+            import :: c_int, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            real(c_double), intent(out) :: quad2(*), nodal(*)
+            integer(c_int64_t), value :: nq2, nn
+        end function hnumo_energy_means
+
+        integer(c_int) function hnumo_energy_end(eng) bind(C, name='hnumo_energy_end')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: eng
+        end function hnumo_energy_end
 
         ! Sample sets (see include/hnumo_engine.h): the device state, or the flow statistics, at
         ! arbitrary points by the element's own Lagrange interpolant -- an output grid, a

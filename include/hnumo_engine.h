@@ -410,6 +410,79 @@ int hnumo_cov_fields(hnumo_engine *eng, double *out, int64_t n);
 int hnumo_cov_integrals(hnumo_engine *eng, double *out, int64_t n);
 int hnumo_cov_end(hnumo_engine *eng);
 
+/* Energy budget on the device state (additive in ABI v10): the power the wind puts into the top layer, the
+ * power the bottom drag removes, the interior viscous dissipation, and the kinetic and available potential
+ * energy these change.  Wind work and drag are products of fields that decorrelate within a few steps, with
+ * a wind that may change on the device every step (hnumo_wind_*), so they are formed where the state and
+ * the wind live -- at the quadrature points, where the model applies its forcing -- and accumulated there.
+ * Definitions (normative; IEEE double, no FMA, every sum left to right from its first product).  Owned
+ * element e, nodes I = e*P + j*ngl + i, quad points Iq = e*Q + jq*nq + iq (nq = 2*ngl - 1, as creation
+ * requires), w_I the nodal jac, wq_Iq the quad weight wjac, tau(1:2,Iq) the wind as it stands on the device
+ * at the time of the sample: what hnumo_wind_get returns; after a scheduled step the row the step used.
+ * At the nodes, per layer k:
+ *   dp = q(1,I,k);  u = q(2,I,k)/dp;  v = q(3,I,k)/dp;  m = dp/gravity            (mass per area)
+ *   ke_k  = (0.5*(u*u + v*v))*m
+ *   z_k   = elevation of layer k's top interface as hnumo_layer_fields forms it (row 5)
+ *   d_k   = z_k - zref(I,k)                                   (zref given at begin; NULL: 0.0)
+ *   c_1   = 0.5*(gravity*(1.0/alpha_1));  c_k = 0.5*(gravity*(1.0/alpha_k - 1.0/alpha_(k-1)))  (k >= 2)
+ *   ape_k = c_k*(d_k*d_k)
+ *   u_x,u_y,v_x,v_y = the element's own gradient, the statements of hnumo_vort, unchanged
+ *   eps_k = (visc_mlswe*((u_x*u_x + u_y*u_y) + (v_x*v_x + v_y*v_y)))*m
+ * At the quad points, node->quad interpolation of a nodal field a(i,j) is done in two passes in this order:
+ *   t(iq,n)  = psiq(1,iq)*a(1,n);  for m = 2..ngl: t = t + psiq(m,iq)*a(m,n)
+ *   A(iq,jq) = psiq(1,jq)*t(iq,1); for n = 2..ngl: A = A + psiq(n,jq)*t(iq,n)
+ * It is applied to u_1, v_1 (top layer) and u_L, v_L, dp_L (bottom layer; for nlayers = 1 the same layer),
+ * giving U1, V1, UL, VL, DPL.  Then
+ *   W = tau(1,Iq)*U1 + tau(2,Iq)*V1
+ *   botfr == 0:  D = +0.0                                         (nothing interpolated for it)
+ *   botfr == 1:  spd = (cd_mlswe/gravity)*DPL
+ *   botfr == 2:  spd = (cd_mlswe/alpha_L)*sqrt(UL*UL + VL*VL)
+ *                tb_u = spd*UL;  tb_v = spd*VL;  D = tb_u*UL + tb_v*VL
+ * Units follow from mod_rhs_btp.F90:171, d(u dp)/dt = gravity*(tau - tb) + ...: tau and tb are stresses,
+ * m = dp/g is mass per area, and W, D, eps are W/m^2.  Sign convention:
+ * d(sum KE + sum APE)/dt ~ W - D - sum eps.
+ * What the terms are and what they are not: the drag law is that of mod_rhs_btp.F90:157-168 evaluated on
+ * the layer state q, not on the sub-cycle's (qb, qprime) split or on its time average; the wind is credited
+ * to the top layer; eps is the interior estimate, without the LDG face terms; the KE<->APE conversion term
+ * is not formed.  The budget therefore closes to discretisation error, not to bits.
+ * One SAMPLE accumulates running sums (plain adds in sample order from +0.0; one lane owns a sum):
+ * S_W += W and S_D += D per quad point, S_V += eps_k per node and layer.  With a series, one sample also
+ * appends 3*nlayers + 2 integrals over the rank's owned elements: KE_1..L, APE_1..L, V_1..L, W, D -- nodal
+ * rows the products w_I*x_I added in node order per element, quad rows wq_Iq*x_Iq in quad order, starting
+ * from the first; the element sums combined by the position-defined pairwise tree of the flow statistics'
+ * series; the host adds the ranks.  No floating-point atomics.  Ghost elements are never visited and read 0.
+ * Every value has the bits of the numpy mirror hnumo/energy.py (HostEnergy).  DESIGN.md §6.1.8.
+ *
+ * hnumo_energy_begin: zref(npoin,nlayers) or NULL: 0.  every and series_capacity as hnumo_stats_begin's:
+ *   every = 0: only hnumo_energy_sample takes samples; every = k >= 1: the engine also takes one after
+ *   every k-th successful hnumo_ti_rk_bcl (hnumo_group_ti_rk_bcl for grouped engines) since begin, once
+ *   the step's abort / retry handling has finished (a step redone after a persistent abort is sampled
+ *   once), after the eddy covariances' sample and before the sample sets and the floats; a step that
+ *   returns non-zero is not sampled.  series_capacity = 0: sums only.  A second call resets.  nlayers 1..3
+ *   and every ngl the engine accepts.
+ * hnumo_energy_sample: one sample now: plain launches on the engine's stream outside the captured step,
+ *   nothing copied back; the step's launches, graph and bits are the same with the observer on or off.
+ * hnumo_energy_series: out(3*nlayers+2, count), n >= (3*nlayers+2)*count; out = NULL returns the count;
+ *   clear != 0 empties the series after the read.
+ * hnumo_energy_sums / hnumo_energy_set_sums: quad2(2,npoin_q) = S_W, S_D, nq2 = 2*npoin_q;
+ *   nodal(npoin,nlayers) = S_V, nn = npoin*nlayers; and the sample count: a restarted run restores them.
+ * hnumo_energy_means: S_W/N, S_D/N and S_V/N, N = double(samples): the maps of mean wind power input, drag
+ *   and dissipation.
+ * hnumo_energy_end: frees the buffers; a no-op before hnumo_energy_begin.  hnumo_engine_destroy frees a
+ *   begun observer.
+ * All return 4, with the call and the value in hnumo_last_error: before hnumo_energy_begin, for a wrong n,
+ * nq2 or nn, a negative every or capacity; a sample returns 4 when the series is full (nothing is
+ * accumulated; the step itself is done) and before any state was uploaded; hnumo_energy_means with no
+ * samples; hnumo_energy_series with no series.                                                     */
+int hnumo_energy_begin(hnumo_engine *eng, const double *zref, int32_t every, int32_t series_capacity);
+int hnumo_energy_sample(hnumo_engine *eng);
+int hnumo_energy_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear);
+int hnumo_energy_sums(hnumo_engine *eng, double *quad2, int64_t nq2, double *nodal, int64_t nn, int64_t *nsamples);
+int hnumo_energy_set_sums(hnumo_engine *eng, const double *quad2, int64_t nq2, const double *nodal, int64_t nn,
+                          int64_t nsamples);
+int hnumo_energy_means(hnumo_engine *eng, double *quad2, int64_t nq2, double *nodal, int64_t nn);
+int hnumo_energy_end(hnumo_engine *eng);
+
 /* Sample sets (additive in ABI v10): the state on the device, or the accumulated flow statistics,
  * evaluated at arbitrary points -- a regular output grid, a cross-section, a few stations -- by the
  * element's own Lagrange interpolant, where the post-processing scripts griddata the synced nodal
