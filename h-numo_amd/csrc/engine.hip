@@ -7,9 +7,9 @@
 // the reference's time loop (kernels_diag.hip: hnumo_diagnostics, hnumo_layer_fields) and the
 // online flow statistics (kernels_stats.hip: hnumo_stats_*), the vorticity products (kernels_vort.hip:
 // hnumo_vort_*), the eddy covariances (kernels_cov.hip: hnumo_cov_*), the energy budget
-// (kernels_energy.hip: hnumo_energy_*), the sample sets (kernels_sample.hip) and the float sets
-// (kernels_float.hip: hnumo_floats_*) are plain launches on the same stream between replays; the host
-// side of those six observers is observers.hip, included below.
+// (kernels_energy.hip: hnumo_energy_*), the region sets (kernels_region.hip: hnumo_regions_*), the sample
+// sets (kernels_sample.hip) and the float sets (kernels_float.hip: hnumo_floats_*) are plain launches on the
+// same stream between replays; the host side of those seven observers is observers.hip, included below.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -31,6 +31,7 @@
 #include "setup_plan.h"
 #include "sample_plan.h"
 #include "float_plan.h"
+#include "region_plan.h"
 #include "kernels_bcl.hip"
 #include "kernels_btp.hip"
 #include "kernels_lapq.hip"
@@ -39,6 +40,7 @@
 #include "kernels_vort.hip"
 #include "kernels_cov.hip"
 #include "kernels_energy.hip"
+#include "kernels_region.hip"
 #include "kernels_sample.hip"
 #include "kernels_float.hip"
 #include "kernels_wind.hip"
@@ -262,6 +264,21 @@ struct hnumo_engine {
     double *d_w = nullptr, *d_out = nullptr;
     Series series;
   } samples[SP_MAXSETS];
+  // region sets (hnumo_regions_*; kernels_region.hip): the host plan (region_plan.h), the member list and
+  // the passes' chunk descriptors on the device, the caller's coriolis_df (NULL: f = 0), the member
+  // partials [V][nmem] with the two level buffers of the segmented tree, the regions' areas and the series
+  // [capacity][V][R].  regions_on: some set is sampled after a step (the one test a step pays)
+  struct RegionSet {
+    bool used = false;
+    int V = 0;
+    RegionPlan plan;
+    int *d_mem = nullptr;
+    RegionChunk *d_desc = nullptr;         // the passes' descriptors, pass after pass
+    double *f = nullptr, *part = nullptr, *lvl[2] = {nullptr, nullptr};
+    std::vector<double> area;              // [R]
+    Series series;
+  } regions[RG_MAXSETS];
+  bool regions_on = false;
   // float sets (hnumo_floats_*): the side neighbours of the owned elements, derived once at create
   // from face / imapl / imapr (fl_nbr_err: why not, reported by hnumo_floats_create); per set the host
   // geometry (float_plan.h), the permutation back to input order, the element tables and the SoA
@@ -1636,6 +1653,7 @@ void hnumo_engine_destroy(hnumo_engine *eng) {
   vort_free(eng);
   cov_free(eng);
   energy_free(eng);
+  for (int id = 0; id < RG_MAXSETS; id++) regions_free(eng, id);
   for (int id = 0; id < SP_MAXSETS; id++) sample_free(eng, id);
   for (int id = 0; id < FL_MAXSETS; id++) floats_free(eng, id);
   wind_free(eng);

@@ -105,19 +105,10 @@ __global__ void __launch_bounds__(ST_BS) stats_accumulate_kernel(StatsArgs a) {
   }
 }
 
-// The pairwise tree over positions.  Workgroup (c, r) reduces the aligned chunk c of ST_CHUNK
-// entries of row r of `in` (n entries per row) to one value, out[r * orow + c]: that value is entry c
-// of level log2(ST_CHUNK) of the whole tree, so a pass over the chunks followed by passes over the
-// results (the last one a single workgroup per row, writing the sample's slot of the series:
-// orow = 1) is the tree of the definition.
-__global__ void __launch_bounds__(ST_BS) stats_tree_kernel(const double *__restrict__ in, int n, double *__restrict__ out,
-                                                           int orow) {
-  __shared__ double x[ST_CHUNK];
-  const int tid = threadIdx.x, c = blockIdx.x, r = blockIdx.y;
-  const int base = c * ST_CHUNK;
-  int m = min(ST_CHUNK, n - base);
-  const double *p = in + (size_t)r * n + base;
-  for (int i = tid; i < m; i += ST_BS) x[i] = p[i];
+// The halving of one chunk: x[0..m) in LDS, m <= ST_CHUNK, filled by the workgroup's ST_BS lanes (the
+// barrier after the fill is taken here); x[0] holds the chunk's value on return, visible to every lane.
+// The one text of the tree: stats_tree_kernel and region_tree_kernel (kernels_region.hip) call it.
+__device__ __forceinline__ void tree_halve(double *x, int m, int tid) {
   __syncthreads();
   while (m > 1) {
     const int h = (m + 1) >> 1;
@@ -137,6 +128,22 @@ __global__ void __launch_bounds__(ST_BS) stats_tree_kernel(const double *__restr
     __syncthreads();
     m = h;
   }
+}
+
+// The pairwise tree over positions.  Workgroup (c, r) reduces the aligned chunk c of ST_CHUNK
+// entries of row r of `in` (n entries per row) to one value, out[r * orow + c]: that value is entry c
+// of level log2(ST_CHUNK) of the whole tree, so a pass over the chunks followed by passes over the
+// results (the last one a single workgroup per row, writing the sample's slot of the series:
+// orow = 1) is the tree of the definition.
+__global__ void __launch_bounds__(ST_BS) stats_tree_kernel(const double *__restrict__ in, int n, double *__restrict__ out,
+                                                           int orow) {
+  __shared__ double x[ST_CHUNK];
+  const int tid = threadIdx.x, c = blockIdx.x, r = blockIdx.y;
+  const int base = c * ST_CHUNK;
+  const int m = min(ST_CHUNK, n - base);
+  const double *p = in + (size_t)r * n + base;
+  for (int i = tid; i < m; i += ST_BS) x[i] = p[i];
+  tree_halve(x, m, tid);
   if (tid == 0) out[(size_t)r * orow + c] = x[0];
 }
 

@@ -1,14 +1,15 @@
 // observers.hip -- what runs after a successful step of the resident state: the online flow
 // statistics (kernels_stats.hip), the vorticity products (kernels_vort.hip), the eddy covariances
-// (kernels_cov.hip), the energy budget (kernels_energy.hip, energy_plan.h), the sample sets
-// (kernels_sample.hip, sample_plan.h) and the float sets (kernels_float.hip, float_plan.h).
+// (kernels_cov.hip), the energy budget (kernels_energy.hip, energy_plan.h), the region sets
+// (kernels_region.hip, region_plan.h), the sample sets (kernels_sample.hip, sample_plan.h) and the float
+// sets (kernels_float.hip, float_plan.h).
 //
 // Part of engine.hip's translation unit: included there once fail, HIPCHK and struct hnumo_engine
 // (with Series and TreeSum) are defined.  All of it is plain launches on the engine stream outside
 // the captured step: the step's launches, graph and bits are the same with or without observers.
 //
 // An observer is a kernel, a Series, an entry in observers_after_step and a free in
-// hnumo_engine_destroy; the pieces below are what the six have in common (the eddy covariances keep
+// hnumo_engine_destroy; the pieces below are what the seven have in common (the eddy covariances keep
 // no series: their `every` stands alone).
 
 // ------------------------------------------------------------------ shared pieces
@@ -820,6 +821,190 @@ extern "C" int hnumo_energy_means(hnumo_engine *eng, double *quad2, int64_t nq2,
   const double N = (double)eng->energy.nsamples;
   for (int64_t x = 0; x < nq2; x++) quad2[x] = quad2[x] / N;
   for (int64_t x = 0; x < nn; x++) nodal[x] = nodal[x] / N;
+  return HNUMO_OK;
+}
+
+// ------------------------------------------------------------------ region sets
+// eng->regions[]: the host plan (region_plan.h), the member list and the passes' descriptors on the device,
+// the member partials [V][nmem] with the two level buffers, the areas and the series [capacity][V][R]
+using RegionSet = hnumo_engine::RegionSet;
+
+static void regions_flag(hnumo_engine *eng) {
+  eng->regions_on = false;
+  for (const auto &s : eng->regions) eng->regions_on = eng->regions_on || (s.used && s.series.every > 0);
+}
+
+static void regions_free(hnumo_engine *eng, int id) {
+  auto &s = eng->regions[id];
+  dfree(s.f, s.part, s.lvl[0], s.lvl[1]);
+  dfree(s.d_mem);
+  dfree(s.d_desc);
+  series_free(s.series);
+  s = RegionSet{};
+  regions_flag(eng);
+}
+
+static RegionSet *regions_set(hnumo_engine *eng, int32_t id, const char *who) {
+  return set_by_id(eng, eng->regions, id, who, "region");
+}
+
+// the passes of the set's plan over `rows` rows of s.part into entry [rows][R]: one launch per pass,
+// whatever the number of regions
+static void regions_tree(hnumo_engine *eng, const RegionSet &s, int rows, double *entry) {
+  const double *in = s.part;
+  const RegionChunk *d = s.d_desc;
+  for (size_t p = 0; p < s.plan.pass.size(); p++) {
+    const RegionPass &ps = s.plan.pass[p];
+    double *next = s.lvl[p & 1];
+    hipLaunchKernelGGL(region_tree_kernel, dim3((unsigned)ps.chunks.size(), rows), dim3(RG_BS), 0, eng->stream, (const int4 *)d, in,
+                       (size_t)ps.nin, next, (size_t)ps.nout, entry, s.plan.R);
+    d += ps.chunks.size();
+    in = next;
+  }
+}
+
+extern "C" int hnumo_regions_create(hnumo_engine *eng, const int32_t *region_of_elem, int64_t n, int32_t nregions, int32_t rows_mask,
+                                    const double *coriolis_df, int32_t every, int32_t series_capacity, int32_t *id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const char *who = "hnumo_regions_create";
+  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
+  if (every < 0 || series_capacity < 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": every and series_capacity must be >= 0, got " + std::to_string(every) +
+                                            ", " + std::to_string(series_capacity));
+  // (with_L and with_ngl dispatch these and no others; hnumo_vort_begin asks the same)
+  if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl (nlayers 1..3; ngl 3, 4, 5, 6 or 8), got " +
+                                            std::to_string(eng->L) + ", " + std::to_string(eng->ngl));
+  RegionPlan pl;
+  if (int rc = region_plan(region_of_elem, n, nregions, rows_mask, eng->nelem_owned, pl, eng->err, who)) return rc;
+  const int slot = free_slot(eng->regions);
+  if (slot < 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the engine holds " + std::to_string(RG_MAXSETS) +
+                                            " region sets already (hnumo_regions_destroy frees one)");
+  HIPCHK(hipSetDevice(eng->device));
+  auto &s = eng->regions[slot];
+  s = RegionSet{};
+  const int V = rg_rows(eng->L, rows_mask), R = pl.R;
+  const size_t nmem = (size_t)pl.nmem(), npoin = (size_t)eng->npoin;
+  std::vector<RegionChunk> desc;
+  for (const RegionPass &ps : pl.pass) desc.insert(desc.end(), ps.chunks.begin(), ps.chunks.end());
+  static_assert(sizeof(RegionChunk) == sizeof(int4), "region_tree_kernel reads a descriptor as one int4");
+  double *d_area = nullptr;
+  bool ok = hipMalloc((void **)&s.d_mem, (nmem ? nmem : 1) * sizeof(int)) == hipSuccess &&
+            hipMalloc((void **)&s.d_desc, desc.size() * sizeof(RegionChunk)) == hipSuccess &&
+            alloc_doubles(&s.part, (size_t)V * nmem) && alloc_doubles(&s.lvl[0], (size_t)V * pl.level_size(0)) &&
+            alloc_doubles(&s.lvl[1], (size_t)V * pl.level_size(1)) && alloc_doubles(&d_area, (size_t)R) &&
+            (!(rows_mask & RG_VORT) || !coriolis_df || alloc_doubles(&s.f, npoin)) &&
+            series_begin(eng, s.series, (size_t)V * R, series_capacity ? every : 0, series_capacity, false) == hipSuccess;
+  ok = ok && (nmem == 0 || hipMemcpy(s.d_mem, pl.members.data(), nmem * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) &&
+       hipMemcpy(s.d_desc, desc.data(), desc.size() * sizeof(RegionChunk), hipMemcpyHostToDevice) == hipSuccess &&
+       (!s.f || hipMemcpy(s.f, coriolis_df, npoin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess);
+  s.V = V;
+  s.plan = std::move(pl);
+  s.area.assign((size_t)R, 0.0);
+  int rc = HNUMO_OK;
+  if (ok) {
+    // the areas: the members' sums of w_I*1.0 in node order into row 0 of part, then the same tree
+    if (nmem > 0) {
+      const int EPB = RG_BS / eng->P;
+      const int nb = (int)std::max<size_t>(1, std::min<size_t>((nmem + EPB - 1) / EPB, 8192));
+      hipLaunchKernelGGL(region_area_kernel, dim3(nb), dim3(RG_BS), 0, eng->stream, eng->nstat + (size_t)NS_W * npoin, s.d_mem,
+                         (int)nmem, eng->ngl, s.part);
+    }
+    regions_tree(eng, s, 1, d_area);
+    ok = hipGetLastError() == hipSuccess;
+    if (ok) rc = download(eng, s.area.data(), d_area, (size_t)R * sizeof(double));
+  }
+  (void)hipFree(d_area);
+  if (!ok || rc) {
+    (void)hipGetLastError();
+    regions_free(eng, slot);
+    return rc ? rc : fail(eng, HNUMO_ERR_DEVICE, std::string(who) + ": device allocation or upload failed");
+  }
+  s.plan.slot = std::vector<int32_t>();   // (the device holds the member list; the passes stay for the launches)
+  s.used = true;
+  regions_flag(eng);
+  *id = slot;
+  return HNUMO_OK;
+}
+
+// one sample of the set into its series, ordered after what is on the engine stream; no copy back
+static int regions_record(hnumo_engine *eng, RegionSet &s, int id, const char *who) {
+  if (!eng->has_state)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (s.series.cap == 0)
+    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": region set " + std::to_string(id) +
+                                            " has no series (hnumo_regions_create was given series_capacity = 0)");
+  if (int rc = series_full(eng, s.series, who, "the series of region set " + std::to_string(id), "samples", "recorded")) return rc;
+  const int nmem = (int)s.plan.nmem(), EPB = RG_BS / eng->P;
+  if (nmem > 0) {
+    RegionArgs a{};
+    a.q = eng->q;
+    a.alpha = eng->alpha;
+    a.nstat = eng->nstat;
+    a.f = s.f;
+    a.dpsi = eng->basis + 2 * (size_t)eng->ngl * eng->nq;
+    a.mem = s.d_mem;
+    a.part = s.part;
+    a.gravity = eng->p.gravity;
+    a.npoin = eng->npoin;
+    a.nmem = nmem;
+    const int nb = std::max(1, std::min((nmem + EPB - 1) / EPB, 8192));
+    with_ngl(eng->ngl, [&](auto ngl) {
+      with_L(eng->L, [&](auto l) {
+        constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
+        switch (s.plan.mask) {
+          case RG_FLOW: hipLaunchKernelGGL((region_accumulate_kernel<NGL, L, RG_FLOW>), dim3(nb), dim3(RG_BS), 0, eng->stream, a); break;
+          case RG_VORT: hipLaunchKernelGGL((region_accumulate_kernel<NGL, L, RG_VORT>), dim3(nb), dim3(RG_BS), 0, eng->stream, a); break;
+          default:
+            hipLaunchKernelGGL((region_accumulate_kernel<NGL, L, RG_FLOW | RG_VORT>), dim3(nb), dim3(RG_BS), 0, eng->stream, a);
+            break;
+        }
+      });
+    });
+  }
+  regions_tree(eng, s, s.V, series_slot(s.series));
+  HIPCHK(hipGetLastError());
+  s.series.count++;
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_regions_sample(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = regions_set(eng, id, "hnumo_regions_sample");
+  if (!s) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  return regions_record(eng, *s, id, "hnumo_regions_sample");
+}
+
+extern "C" int hnumo_regions_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  auto *s = regions_set(eng, id, "hnumo_regions_series");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (s->series.cap == 0)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_regions_series: region set " + std::to_string(id) +
+                                            " has no series (hnumo_regions_create was given series_capacity = 0)");
+  return series_read(eng, s->series, s->V, (size_t)s->plan.R, out, n, count, clear, "hnumo_regions_series", "V*nregions");
+}
+
+extern "C" int hnumo_regions_area(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  const auto *s = regions_set(eng, id, "hnumo_regions_area");
+  if (!s) return HNUMO_ERR_INVALID;
+  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_regions_area: out is NULL");
+  if (n != s->plan.R)
+    return fail(eng, HNUMO_ERR_INVALID, "hnumo_regions_area: n must be the set's nregions = " + std::to_string(s->plan.R) + ", got " +
+                                            std::to_string(n));
+  std::memcpy(out, s->area.data(), (size_t)n * sizeof(double));
+  return HNUMO_OK;
+}
+
+extern "C" int hnumo_regions_destroy(hnumo_engine *eng, int32_t id) {
+  if (!eng) return HNUMO_ERR_INVALID;
+  if (!regions_set(eng, id, "hnumo_regions_destroy")) return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the set's tables)
+  regions_free(eng, id);
   return HNUMO_OK;
 }
 
@@ -1718,7 +1903,7 @@ extern "C" int hnumo_floats_settle(hnumo_engine *eng, int32_t id) {
 // ------------------------------------------------------------------ after a successful step
 // Called once run_steps has returned 0 (so a step redone on per-stage launches is observed once), in
 // this order: the statistics' sample; the vorticity series' sample; the eddy covariances' sample; the
-// energy budget's sample; the sample sets' recordings, which see the new sums of a set on the statistics or the covariances; the
+// energy budget's sample; the region sets' samples; the sample sets' recordings, which see the new sums of a set on the statistics or the covariances; the
 // float sets' advance by params.dt, last.  Every
 // observer runs whatever the others return (a float cannot skip a step because a series was full);
 // the first non-zero code is returned.
@@ -1735,6 +1920,11 @@ static int observers_after_step(hnumo_engine *eng) {
     run(cov_sample(eng, "eddy covariances after the step (the step itself succeeded)"));
   if (eng->energy.on && series_due(eng->energy.series))
     run(energy_sample(eng, "energy budget after the step (the step itself succeeded)"));
+  if (eng->regions_on)
+    for (int id = 0; id < RG_MAXSETS; id++) {
+      auto &s = eng->regions[id];
+      if (s.used && series_due(s.series)) run(regions_record(eng, s, id, "region series after the step (the step itself succeeded)"));
+    }
   for (int id = 0; id < SP_MAXSETS; id++) {
     auto &s = eng->samples[id];
     if (s.used && series_due(s.series)) run(sample_record(eng, s, id, "sample series after the step (the step itself succeeded)"));

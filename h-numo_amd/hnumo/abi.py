@@ -137,6 +137,24 @@ def declare_energy(L):
     L.hnumo_energy_end.argtypes = [vp]
 
 
+REGION_MAXSETS, REGION_FLOW, REGION_VORT = 4, 1, 2    # HNUMO_REGION_MAXSETS, HNUMO_REGION_FLOW, HNUMO_REGION_VORT
+
+
+def region_rows(nlayers: int, mask: int) -> int:
+    """V: the rows of a region set's entry."""
+    return (4 * nlayers if mask & REGION_FLOW else 0) + (3 * nlayers if mask & REGION_VORT else 0)
+
+
+def declare_regions(L):
+    """The region sets' calls of the loaded library L (hnumo_regions_*)."""
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.hnumo_regions_create.argtypes = [vp, _ip, i64, i32, i32, _dp, i32, i32, _ip]
+    L.hnumo_regions_sample.argtypes = [vp, i32]
+    L.hnumo_regions_series.argtypes = [vp, i32, _dp, i64, C.POINTER(i64), i32]
+    L.hnumo_regions_area.argtypes = [vp, i32, _dp, i64]
+    L.hnumo_regions_destroy.argtypes = [vp, i32]
+
+
 def ptr(a: np.ndarray | None):
     """Pointer to a contiguous Fortran-order array (keeps no reference: caller owns it)."""
     if a is None:

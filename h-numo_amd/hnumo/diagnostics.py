@@ -282,7 +282,8 @@ def restart_state(case, path):
 def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_restart=None,
               lcheck_conserved=True, lprint_diagnostics=True, time_initial=0.0, restart_file_number=0,
               time_scale=1.0, out=None, device_diagnostics=False, flow_stats=None, stats_every=1, floats=None,
-              vorticity=None, vort_every=1, wind=None, eddy_cov=None, cov_every=1, energy=None, energy_every=1):
+              vorticity=None, vort_every=1, wind=None, eddy_cov=None, cov_every=1, energy=None, energy_every=1,
+              regions=None, regions_every=1):
     """mod_time_loop.F90:61-269 around stepper.ti_rk_bcl (a hnumo.engine.Engine, resident, or
     in tests the CPU oracle).  Writes the mlswe#### snapshots (dump_data, every
     nint(time_restart/dt) steps), mass_mlswe.cons (lcheck_conserved) and mlswe_FIN.txt into
@@ -328,7 +329,16 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
     step of this loop (after eddy_cov's sample, before the floats) it gets add(q, tau).  The device object
     (begun with every = 0) samples the state and the wind where they live (no sync); the host object reads
     the host arrays and is given the wind that `wind` blended for that step (wind.tau; None without `wind`:
-    the case's own tau_wind).  None: nothing changes."""
+    the case's own tau_wind).  None: nothing changes.
+
+    regions: a hnumo.regions.DeviceRegions or HostRegions (or a list of them: overlapping partitions are
+    separate sets), handled like flow_stats: after every regions_every-th step of this loop (after the
+    energy's sample, before the floats) each gets add(q).  The device object (created with every = 0) samples
+    the engine's state where it lives (q is ignored, no sync); the host object reads the host arrays, which
+    a resident stepper syncs for it first.  None: nothing changes."""
+    region_sets = [] if regions is None else list(regions) if isinstance(regions, (list, tuple)) else [regions]
+    if region_sets and int(regions_every) < 1:
+        raise ValueError("regions_every must be >= 1")
     if energy is not None and int(energy_every) < 1:
         raise ValueError("energy_every must be >= 1")
     if eddy_cov is not None and int(cov_every) < 1:
@@ -415,6 +425,11 @@ def time_loop(case, stepper, time_final, *, out_dir=".", dump_data=False, time_r
             if resident and on_host:
                 stepper.sync(q, qb, qp)
             energy.add(q, wind.tau if on_host and wind is not None else None)
+        if region_sets and nstep % int(regions_every) == 0:
+            for rs in region_sets:
+                if resident and getattr(rs, "needs_host_state", True):
+                    stepper.sync(q, qb, qp)
+                rs.add(q)
         for fs in float_sets:
             if resident and getattr(fs, "needs_host_state", True):
                 stepper.sync(q, qb, qp)

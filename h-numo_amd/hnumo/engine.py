@@ -111,6 +111,7 @@ def lib():
         abi.declare_float_sensors(L)
         abi.declare_cov(L)
         abi.declare_energy(L)
+        abi.declare_regions(L)
         L.hnumo_wind_begin.argtypes = [vp, dp, i64, i32]
         L.hnumo_wind_set.argtypes = [vp, dp, i32]
         L.hnumo_wind_schedule.argtypes = [vp, dp, i32, i32, i32, i32]
@@ -536,6 +537,44 @@ class Engine:
 
     def energy_end(self):
         self._check(lib().hnumo_energy_end(self.h))
+
+    # ---- region sets on the device state (hnumo_regions_*; mirror and helpers: hnumo/regions.py)
+    def regions_create(self, labels, nregions: int, rows: int = abi.REGION_FLOW, coriolis_df=None, every: int = 0,
+                       series: int = 0) -> int:
+        """A set from labels (nelem_owned) in 0..nregions (0: in no region); rows: abi.REGION_FLOW, REGION_VORT or
+        their sum; coriolis_df (npoin), or None: f = 0.  every = k >= 1: the engine samples after every k-th
+        successful step; series: samples the series can hold.  Returns its id."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        fp = None
+        if coriolis_df is not None:
+            f = np.ascontiguousarray(np.asarray(coriolis_df, dtype=np.float64).reshape(-1))
+            if f.size != self.dims["npoin"]:
+                raise ValueError(f"coriolis_df: {f.size} elements, expected {self.dims['npoin']}")
+            fp = f.ctypes.data_as(C.POINTER(C.c_double))
+        sid = C.c_int32(-1)
+        self._check(lib().hnumo_regions_create(self.h, lab.ctypes.data_as(C.POINTER(C.c_int32)), lab.size, int(nregions), int(rows),
+                                               fp, int(every), int(series), C.byref(sid)))
+        self._sets("region")[sid.value] = (int(nregions), abi.region_rows(self.dims["nlayers"], int(rows)))
+        return sid.value
+
+    def regions_sample(self, sid: int):
+        """Append one sample to the set's series on the device; nothing is copied back."""
+        self._check(lib().hnumo_regions_sample(self.h, int(sid)))
+
+    def regions_series(self, sid: int, clear: bool = False):
+        """(V, nregions, count): the recorded samples; clear empties the series afterwards."""
+        R, V = self._set_sizes("region", sid)
+        return self._series(lib().hnumo_regions_series, (V, R), int(sid), clear=clear)
+
+    def regions_area(self, sid: int):
+        """(nregions,): the sum of the nodal jac per region."""
+        out = np.zeros(self._set_sizes("region", sid)[0])
+        self._check(lib().hnumo_regions_area(self.h, int(sid), _dp(out), out.size))
+        return out
+
+    def regions_destroy(self, sid: int):
+        self._check(lib().hnumo_regions_destroy(self.h, int(sid)))
+        self._sets("region").pop(sid, None)
 
     # ---- sample sets on the device state (hnumo_sample_*; mirror and helpers: hnumo/sample.py)
     def _sample_nval(self, source: int) -> int:

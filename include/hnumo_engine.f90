@@ -92,6 +92,7 @@ module hnumo_engine_c
         hnumo_cov_integrals, hnumo_cov_end, &
         hnumo_energy_begin, hnumo_energy_sample, hnumo_energy_series, hnumo_energy_sums, hnumo_energy_set_sums, &
         hnumo_energy_means, hnumo_energy_end, &
+        hnumo_regions_create, hnumo_regions_sample, hnumo_regions_series, hnumo_regions_area, hnumo_regions_destroy, &
         hnumo_sample_create, hnumo_sample_create_ref, hnumo_sample_plan, hnumo_sample, &
         hnumo_sample_series_begin, hnumo_sample_record, hnumo_sample_series, hnumo_sample_destroy, &
         hnumo_floats_create, hnumo_floats_get, hnumo_floats_plan, hnumo_floats_set, hnumo_floats_advance, &
@@ -102,6 +103,7 @@ module hnumo_engine_c
     integer(c_int32_t), parameter, public :: HNUMO_DIAG_MASS = 1   ! hnumo_diagnostics flags
     integer(c_int32_t), parameter, public :: HNUMO_SAMPLE_STATE = 0, HNUMO_SAMPLE_STATS = 1, &
         HNUMO_SAMPLE_VORT = 2, HNUMO_SAMPLE_COV = 3   ! sample set sources
+    integer(c_int32_t), parameter, public :: HNUMO_REGION_MAXSETS = 4, HNUMO_REGION_FLOW = 1, HNUMO_REGION_VORT = 2
     integer(c_int32_t), parameter, public :: HNUMO_WIND_MAXM = 4, HNUMO_WIND_HOLD = 0, HNUMO_WIND_REPEAT = 1
     integer(c_int32_t), parameter, public :: HNUMO_FLOAT_ACTIVE = 0, HNUMO_FLOAT_LEFT = 1, HNUMO_FLOAT_LOST = 2   ! float status
     integer(c_int32_t), parameter, public :: HNUMO_FLOAT_SENSE_STATE = 1, HNUMO_FLOAT_SENSE_VORT = 2   ! sensor mask bits
@@ -473,6 +475,52 @@ module hnumo_engine_c
             import :: c_int, c_ptr
             type(c_ptr), value :: eng
         end function hnumo_energy_end
+
+        ! Region sets (see include/hnumo_engine.h): the integral series of parts of the rank's domain, many
+        ! regions reduced at once on the device.  region_of_elem(n), n = nelem_owned, labels 0..nregions (0: in
+        ! no region); rows_mask: HNUMO_REGION_FLOW, HNUMO_REGION_VORT or their sum; coriolis_df: c_loc of
+        ! coriolis_df(npoin) or c_null_ptr (f = 0).  every = k >= 1: the engine samples after every k-th
+        ! successful hnumo_ti_rk_bcl itself; series_capacity: samples the series can hold.
+        integer(c_int) function hnumo_regions_create(eng, region_of_elem, n, nregions, rows_mask, coriolis_df, every, &
+                series_capacity, id) bind(C, name='hnumo_regions_create')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr
+            type(c_ptr), value :: eng, coriolis_df
+            integer(c_int32_t), intent(in) :: region_of_elem(*)
+            integer(c_int64_t), value :: n
+            integer(c_int32_t), value :: nregions, rows_mask, every, series_capacity
+            integer(c_int32_t), intent(out) :: id
+        end function hnumo_regions_create
+
+        integer(c_int) function hnumo_regions_sample(eng, id) bind(C, name='hnumo_regions_sample')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+        end function hnumo_regions_sample
+
+        ! out(V, nregions, count), V = 4*nlayers*[FLOW] + 3*nlayers*[VORT]; out: c_loc of the array, or
+        ! c_null_ptr for the count alone
+        integer(c_int) function hnumo_regions_series(eng, id, out, n, count, clear) bind(C, name='hnumo_regions_series')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr
+            type(c_ptr), value :: eng, out
+            integer(c_int32_t), value :: id, clear
+            integer(c_int64_t), value :: n
+            integer(c_int64_t), intent(out) :: count
+        end function hnumo_regions_series
+
+        ! out(nregions): the sum of the nodal jac per region
+        integer(c_int) function hnumo_regions_area(eng, id, out, n) bind(C, name='hnumo_regions_area')
+            import :: c_int, c_int32_t, c_int64_t, c_ptr, c_double
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+            real(c_double), intent(out) :: out(*)
+            integer(c_int64_t), value :: n
+        end function hnumo_regions_area
+
+        integer(c_int) function hnumo_regions_destroy(eng, id) bind(C, name='hnumo_regions_destroy')
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value :: eng
+            integer(c_int32_t), value :: id
+        end function hnumo_regions_destroy
 
         ! Sample sets (see include/hnumo_engine.h): the device state, or the flow statistics, at
         ! arbitrary points by the element's own Lagrange interpolant -- an output grid, a

@@ -483,6 +483,71 @@ int hnumo_energy_set_sums(hnumo_engine *eng, const double *quad2, int64_t nq2, c
 int hnumo_energy_means(hnumo_engine *eng, double *quad2, int64_t nq2, double *nodal, int64_t nn);
 int hnumo_energy_end(hnumo_engine *eng);
 
+/* Region sets (additive in ABI v10): the integral series of PARTS of the rank's domain -- subpolar against
+ * subtropical gyre, the western boundary strip against the interior, zonal strips whose per-layer
+ * meridional transport, cumulated over the layers, is the overturning streamfunction in layer space --
+ * formed where the state lives, by a segmented tree reduction: many regions at once, each with its own
+ * position-defined tree, in a number of launches that does not grow with the number of regions.
+ * Definitions (normative; the same text in csrc/region_plan.h, csrc/kernels_region.hip
+ * and hnumo/regions.py).  A region set labels every owned element with a region r in 0..R; label 0: the
+ * element is in no region.  Up to HNUMO_REGION_MAXSETS = 4 sets exist at once (overlapping partitions,
+ * such as strips and basins, are separate sets).  The members of region r, in ascending local element
+ * number, have local positions 0..n_r-1.  IEEE double, -ffp-contract=off: no FMA; IEEE division; every sum
+ * left to right from its first product.  Per member element e, layer k, node I = e*P + j*ngl + i, w_I the
+ * nodal jac:
+ *   FLOW rows (HNUMO_REGION_FLOW, mask bit 0), the statements of hnumo_stats_*:
+ *     dp = q(1); h = (alpha_k/gravity)*dp; u = q(2)/dp; v = q(3)/dp
+ *     VOL_k = int h;  TU_k = int (u*h);  TV_k = int (v*h);  KE_k = int ((0.5*(u*u+v*v))*h)
+ *   VORT rows (HNUMO_REGION_VORT, mask bit 1), the statements of hnumo_vort_*; f the caller's
+ *   coriolis_df, 0 for NULL:
+ *     Z_k = int ((0.5*(zeta*zeta))*h);  PZ_k = int ((0.5*(pv*pv))*h);  G_k = int zeta
+ * `int` in two steps: per element the products w_I*x_I added in node order from the first product; per
+ * region the element sums combined by the flow statistics' pairwise tree over the LOCAL POSITIONS (entry i
+ * of the next level is x[2i] + x[2i+1], or x[2i] alone where 2i+1 does not exist).  An empty region reads
+ * +0.0 in every row.  No floating-point atomics.  Ghost elements are never members.
+ * Entry: (V, R), V = 4*nlayers*[FLOW] + 3*nlayers*[VORT]; FLOW rows first, 4(k-1) + {0 VOL, 1 TU, 2 TV,
+ * 3 KE}, then the VORT rows, 3(k-1) + {0 Z, 1 PZ, 2 G} (hnumo_vort_series' order).  A set whose only region
+ * holds all owned elements has local position = element position: its KE_k, VOL_k are the bits of
+ * hnumo_stats_series, its Z_k, PZ_k, G_k those of hnumo_vort_series.  Every value has the bits of the numpy
+ * mirror hnumo/regions.py (HostRegions).
+ * Out of scope: labels per node (strips finer than an element; sample sets cover lines); fluxes across
+ * region boundaries (they need the step's own face fluxes); combining ranks (the host adds them, as for the
+ * other series).
+ *
+ * hnumo_regions_create: region_of_elem(n), n = nelem_owned, labels 0..nregions; rows_mask as above;
+ *   coriolis_df(npoin) or NULL (read with HNUMO_REGION_VORT only).  every = 0: only hnumo_regions_sample
+ *   takes samples; every = k >= 1: the engine also takes one after every k-th successful hnumo_ti_rk_bcl
+ *   (hnumo_group_ti_rk_bcl for grouped engines) since create, once the step's abort / retry handling has
+ *   finished (a step redone after a persistent abort is sampled once), after the energy budget's sample and
+ *   before the sample sets and the floats; a step that returns non-zero is not sampled.  series_capacity:
+ *   samples the series can hold.  The regions' areas are formed here, once.  An engine that creates no set
+ *   launches what it launched before.
+ * hnumo_regions_sample: one sample now into the series: one launch over the set's member elements (cost
+ *   follows the members, not the mesh) and ceil(log_1024 max_r n_r) >= 1 tree launches, whatever nregions
+ *   is; plain launches on the engine's stream outside the captured step, nothing copied back; the step's
+ *   launches, graph and bits are the same with or without region sets.
+ * hnumo_regions_series: out(V, nregions, count), n >= V*nregions*count; out = NULL returns the count;
+ *   clear != 0 empties the series after the read.
+ * hnumo_regions_area: out(nregions), n = nregions: sum of w_I per region, by the same per-element order and
+ *   the same tree with x = 1.0.
+ * hnumo_regions_destroy: frees the set; hnumo_engine_destroy frees what is left.
+ * All return 4, with the call and the value in hnumo_last_error: for an unknown id; hnumo_regions_create,
+ * checked in this order, for id NULL, a negative every or capacity, unsupported nlayers or ngl (nlayers
+ * 1..3; ngl 3, 4, 5, 6 or 8: what hnumo_vort_begin accepts), region_of_elem NULL, nregions < 1,
+ * n != nelem_owned, a rows_mask that is empty or holds other bits, a label outside 0..nregions, a fifth set;
+ * a sample before any state was uploaded, on a set with capacity 0, or when the series is full (nothing is
+ * recorded; the step itself is done); hnumo_regions_series on a set with capacity 0 or with too small an
+ * n; hnumo_regions_area with n != nregions.                                                         */
+#define HNUMO_REGION_MAXSETS 4
+#define HNUMO_REGION_FLOW 1
+#define HNUMO_REGION_VORT 2
+int hnumo_regions_create(hnumo_engine *eng, const int32_t *region_of_elem, int64_t n, int32_t nregions, int32_t rows_mask,
+                         const double *coriolis_df, int32_t every, int32_t series_capacity, int32_t *id);
+int hnumo_regions_sample(hnumo_engine *eng, int32_t id);
+int hnumo_regions_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear);
+int hnumo_regions_area(hnumo_engine *eng, int32_t id, double *out, int64_t n);
+int hnumo_regions_destroy(hnumo_engine *eng, int32_t id);
+
 /* Sample sets (additive in ABI v10): the state on the device, or the accumulated flow statistics,
  * evaluated at arbitrary points -- a regular output grid, a cross-section, a few stations -- by the
  * element's own Lagrange interpolant, where the post-processing scripts griddata the synced nodal
