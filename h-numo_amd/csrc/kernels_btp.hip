@@ -48,10 +48,17 @@ constexpr int PRIO_B = 1, PRIO_S = 2, PRIO_E = 3;
 // physics): StageArgs::dbg phase switches -- 1 the face lifts of the volume sums, 2 the Laplacian,
 // 4 the volume sums, 16 the persistent trace waits, 32 the time averages (engine), 64 the term
 // tasks, 128 A2 interpolations, 256 B quad-point tasks, 512 B face tasks, 1024 B nodal tasks,
-// 2048 E2 trace stores, 4096 the A copies of the records (tools/dbg_sweep.py, tools/pmc_ablate.sh)
+// 2048 E2 trace stores, 4096 the A copies of the records, 8192 the persistent stages' re-fetch of
+// the B inputs (tools/dbg_sweep.py, tools/pmc_ablate.sh); 16384, no switch but a mode of the phase
+// clocks: the non-slim persistent bodies split E into its parts (ESPLIT, see the end of stage_body)
 // -- and StageArgs::prof, the per-element phase clocks (tools/stage_profile.py)
 #define DBG(bit) (HNUMO_DIAG && (a.dbg & (bit)))
 #define PROF (HNUMO_DIAG && a.prof)
+// A/B builds only: -DHNUMO_REFETCH_IDLE=0 issues the persistent stages' re-fetch of the B inputs from
+// all four waves, as it was before StageCfg::IDLEB
+#ifndef HNUMO_REFETCH_IDLE
+#define HNUMO_REFETCH_IDLE 1
+#endif
 #define SETPRIO_IF(cond, hi, lo)        \
   do {                                  \
     if (cond)                           \
@@ -264,8 +271,9 @@ struct StageCfg {
                        W_END = O_QN + ((SLIM || LEAN) ? 0 : 4 * P),
                        O_BIN = ev((SF && O_Y + NYV * NGL * NQ > W_END) ? O_Y + NYV * NGL * NQ : W_END);
   // B inputs: the bottom-layer qprime, face statics, neighbour traces, face coefficients,
-  // reloaded every stage (the persistent kernel: re-fetched behind E1) and overlaid by term
-  // buffer 1 once B and the LDG fluxes (D0) are done.  (SLIM: the qprime of A2 in the
+  // reloaded every stage (the persistent kernel: re-fetched behind D, in front of E1, by the waves
+  // that E1 leaves idle where IDLEB holds) and overlaid by term buffer 1 once B and the LDG fluxes
+  // (D0) are done.  (SLIM: the qprime of A2 in the
   // nodal-gradient slot, written only from B on)
   static constexpr int B_QP = 0, B_EF = ev(B_QP + (SLIM ? 0 : 3 * P)), B_TR = B_EF + 4 * FBLK, B_EC = B_TR + 32 * NGL,
                        B_SIZE = B_EC + 4 * EFC, O_B = O_BIN;
@@ -315,6 +323,12 @@ struct StageCfg {
   // (LEAN: the rhs is written only in the last D phase, by the VSUM lanes)
   static_assert(!LEAN || (VSUM && TSZ >= 32 * NQ && TSZ >= 5 * P && 3 * P <= 64 * EW + 64), "LEAN layout");
   static constexpr int TB_LAST = (NCH & 1) ? 0 : TB0, TB_PREV = (NCH & 1) ? TB0 : 0;
+  // IDLEB (persistent sub-cycle, 256-thread exact-sum arenas, where E1 runs on wave 0 alone): the
+  // re-fetch of the next stage's B inputs behind D is issued by waves 1..3, idle during E1, and not
+  // by the E1 wave, which so neither spends its first ~220 instructions on the copies' addresses nor
+  // waits for them (its Laplacian operands come through a flat load, whose vmcnt(0) counted the
+  // copies issued before it) -- see the end of D in stage_body
+  static constexpr bool IDLEB = HNUMO_REFETCH_IDLE && !SF && !SLIM && !LEAN && BS == 256;
   // REGACC (persistent sub-cycle): every accumulating task (quad point, face quad point, node,
   // LDG face node) has its own thread, the same in every stage, so the time averages can live in
   // that thread's registers for the whole launch and be written once, scaled, at the end
@@ -529,6 +543,12 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   // (persistent, later stages: zeroed behind the previous stage's clocks, see the end of the body)
   if (PROF && tid == 0 && (!PERSIST || first)) s_prof[22] = 0;
   if (PROF && tid == 0 && PERSIST && !C::SLIM && first) s_prof[28] = 0;
+  // ESPLIT (dbg 16384; persistent, non-slim): E in its parts.  Slots 32-36 (LDS only) hold a stage's
+  // clocks -- E1 done (thread 0), the last wave's gradient done, the last wave past its wait for the
+  // re-fetched B inputs, the longest such wait, the head of the last D phase -- and slots 12-15, 6
+  // and 7, which then carry no clocks of their own, their sums over the stages (end of the body)
+  const bool ESP = PROF && PERSIST && !C::SLIM && DBG(16384);
+  if (ESP && tid == 0 && first) s_prof[33] = s_prof[34] = s_prof[35] = s_prof[36] = 0;
   const bool use_q0 = !a.rhs_only && a.a1 != 0.0, use_q2 = !a.rhs_only && a.a3 != 0.0;
   const int qpm = (SF || !m.botfr || !a.qpq) ? 0 : a.qpq_mode;  // see StageArgs::qpq
   if (!DBG(4096)) {
@@ -558,7 +578,8 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       }
     }
     // qprime, the face statics and the face coefficients are constant over a sub-cycle
-    // (persistent: the previous stage re-fetched them in E1, see there)
+    // (persistent: the previous stage re-fetched them behind its D phases, in front of its E1, see
+    // there)
     if (!PERSIST || first) {
       if (m.botfr && qpm != 2)
         glds_copy<BS, C::G16>(a.qprime + (size_t)(m.L - 1) * 3 * npoin + (size_t)e * 3 * P, s_qp, 6 * P, tid, rot);
@@ -603,9 +624,9 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     load_pre();
     __syncthreads();  // the async LDS copies have landed
   } else {
-    // persistent, later stages: nothing to wait for.  The B inputs re-fetched in the previous
-    // stage's E1 landed before its barrier in front of E2 (each wave waited for its own copies
-    // there), the state is in place, and no wave waits for the acknowledgement of the trace
+    // persistent, later stages: nothing to wait for.  The B inputs the previous stage re-fetched
+    // behind its D phases landed before its barrier in front of E2 (each wave waited for its own
+    // copies there), the state is in place, and no wave waits for the acknowledgement of the trace
     // granules it has just stored: they stay in flight behind the interpolation.  (The slim N=7
     // arena keeps its wait and barrier here, and the full barrier of the stage loop: without them
     // dg25N7L3 measured 0.5 % slower, EXPERIMENTS.md §1.)
@@ -1223,7 +1244,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       }
     }
   }
-  if (PROF && (tid & 63) == 0) s_prof[12 + (tid >> 6)] = clock64();
+  if (PROF && !ESP && (tid & 63) == 0) s_prof[12 + (tid >> 6)] = clock64();
   LDS_BARRIER();
   STAGE_MARK(2);
 
@@ -1758,6 +1779,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     for (int k = 0; k <= NCH; k++) {
       asm volatile("" ::: "memory");  // keep LDS reads inside their phase (no hoisting)
       if (k == NCH) __builtin_amdgcn_s_setprio(PRIO_E);
+      if (ESP && k == NCH && tid == 0) s_prof[36] = clock64();
       const int WT = (k < NCH) ? ((k == NCH - 1) ? (Q - k * QC) : QC) * NGL : 0;  // term tasks
       if constexpr (VSUM) {
         // first node halves on [0, WT), second halves on [WTMAX, WTMAX + WT)
@@ -1772,22 +1794,35 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
       if (k == 0) for_tasks<BS>(tid, C::OL, 4 * NGL, ldg_task);
       if (k == NCH && !DBG(2)) for_tasks<BS>(tid, 0, 2 * P, [&](int t, bool) { lap_task(t / P, t % P); });
       LDS_BARRIER();
-      if (k < (PERSIST ? 2 : 6)) STAGE_MARK(6 + k);  // (persistent: slots 8-11 accumulate the phases)
+      if (k < (PERSIST ? 2 : 6) && !ESP) STAGE_MARK(6 + k);  // (persistent: slots 8-11 accumulate the phases)
     }
   }
   STAGE_MARK(3);
 
   // persistent: the term buffers are dead now, so the next stage's
   // bottom-layer qprime, face statics and face coefficients (constant over the sub-cycle,
-  // overlaid by term buffer 1 in D1..D2) are re-fetched here, behind E1/E2, instead of at
+  // overlaid by term buffer 1 in D1..D2) are re-fetched here, in front of E1, instead of at
   // the start of the next stage (the traces' slot is not touched: A2 of the next stage
-  // fills it)
+  // fills it).  IDLEB: by waves 1..3 alone, the same chunks from the same addresses to the same
+  // words, rotated over three waves instead of four -- which wave issues a chunk does not change
+  // where it lands -- while wave 0 goes straight into E1 with nothing of its own in flight.  Each
+  // issuing wave waits for its copies in front of E2's barrier, as before; no wave has another
+  // vector-memory operation in flight from here to that wait (the granule load was consumed
+  // before B, the state and trace stores and the averages' write-out follow it).
   if constexpr (PERSIST) {
-    if (a.write_trace) {  // a next stage follows
+    if (a.write_trace && !DBG(8192)) {  // a next stage follows
       int rot = 0;
+      if constexpr (C::IDLEB) {
+        if (tid >= 64) {
+          if (m.botfr && qpm == 0) glds_copy<BS - 64, C::G16>(a.qprime + (size_t)(m.L - 1) * 3 * npoin + (size_t)e * 3 * P, s_qp, 6 * P, tid - 64, rot);
+          glds_copy<BS - 64, C::G16>(m.efstat + (size_t)e * 4 * C::FBLK, s_ef, 2 * 4 * C::FBLK, tid - 64, rot);
+          glds_copy<BS - 64, C::G16>(a.efcoef + (size_t)e * 4 * C::EFC, s_ec, 2 * 4 * C::EFC, tid - 64, rot);
+        }
+      } else {
       if (!C::SLIM && m.botfr && qpm == 0) glds_copy<BS, C::G16>(a.qprime + (size_t)(m.L - 1) * 3 * npoin + (size_t)e * 3 * P, s_qp, 6 * P, tid, rot);
       glds_copy<BS, C::G16>(m.efstat + (size_t)e * 4 * C::FBLK, s_ef, 2 * 4 * C::FBLK, tid, rot);
       glds_copy<BS, C::G16>(a.efcoef + (size_t)e * 4 * C::EFC, s_ec, 2 * 4 * C::EFC, tid, rot);
+      }
     }
   }
 
@@ -1855,6 +1890,7 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
     s_v[p] = qn[3] / qn[0];
   }
   if (a.rhs_only) return;
+  if (ESP && tid == 0) s_prof[32] = clock64();
   if (a.write_trace && EW0 == 0 && BS == 256) {
     // the new state's grad(u_bar) on four waves, one component each (nodal_grad: the same terms
     // and order as nodal_grad4's), after a barrier, instead of on the E1 wave alone
@@ -1881,8 +1917,17 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
   // persistent: each wave's LDS-DMA copies of the re-fetch above have landed before it passes the
   // barrier, which so also orders them before their readers in the next stage.  Only they are
   // outstanding here -- the wait comes before this stage's first trace store, and nothing waits for
-  // those.  (Not the slim arena: it waits at the head of the next stage, see there.)
+  // those.  (Where all four waves issue the copies, the E1 wave has waited already: its Laplacian
+  // operands, a.lapq or s_lap, come through one flat load, whose own vmcnt(0) counts the copies
+  // issued before it.  Not the slim arena: it waits at the head of the next stage, see there.)
+  unsigned long long esp_g = 0;
+  if (ESP && (tid & 63) == 0) atomicMax(&s_prof[33], esp_g = clock64());
   if constexpr (PERSIST && !C::SLIM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (ESP && (tid & 63) == 0) {
+    const unsigned long long cw = clock64();
+    atomicMax(&s_prof[34], cw);
+    atomicMax(&s_prof[35], cw - esp_g);
+  }
   LDS_BARRIER();
   STAGE_MARK(4);
 
@@ -1952,6 +1997,16 @@ __device__ __forceinline__ void stage_body(const ARGS &a, double *s_arena, unsig
         else
           s_prof[29] += s_prof[5] - s_prof[4];  // (non-slim: E2, the trace stores)
         s_prof[27] += s_prof[22];
+        if (ESP) {  // E1 | the gradient and its barrier | the wait (last wave) | E2's barrier; the last D phase; the longest wait
+          if (first) s_prof[12] = s_prof[13] = s_prof[14] = s_prof[15] = s_prof[6] = s_prof[7] = 0;
+          s_prof[12] += s_prof[32] - s_prof[3];
+          s_prof[13] += s_prof[33] - s_prof[32];
+          s_prof[14] += s_prof[34] - s_prof[33];
+          s_prof[15] += s_prof[4] - s_prof[34];
+          s_prof[6] += s_prof[3] - s_prof[36];
+          s_prof[7] += s_prof[35];
+          s_prof[35] = 0;
+        }
         s_prof[24] += s_prof[21] - s_prof[0];
         s_prof[25] += s_prof[5] - s_prof[21];
         s_prof[26] += 1;
@@ -1968,7 +2023,7 @@ template <int NGL, int NQ, bool SF, int NB = 0, int ACCF = 0>
 __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF, NB>::BS), (StageCfg<NGL, NQ, SF, NB>::MINW))
     btp_stage_kernel(StageArgs a) {
   __shared__ __attribute__((aligned(16))) double s_arena[StageCfg<NGL, NQ, SF, NB>::ARENA];
-  __shared__ unsigned long long s_prof[HNUMO_DIAG ? 32 : 1];
+  __shared__ unsigned long long s_prof[HNUMO_DIAG ? 40 : 1];
   stage_body<NGL, NQ, SF, false, StageArgs, NB, ACCF>(a, s_arena, s_prof,
                                                       a.elist ? a.elist[blockIdx.x] : (int)blockIdx.x, threadIdx.x);
 }
@@ -2035,7 +2090,7 @@ __global__ void __launch_bounds__((StageCfg<NGL, NQ, SF>::BS), (StageCfg<NGL, NQ
     btp_subcycle_kernel(SubArgs sa) {
   using C = StageCfg<NGL, NQ, SF>;
   __shared__ __attribute__((aligned(16))) double s_arena[C::ARENA];
-  __shared__ unsigned long long s_prof[HNUMO_DIAG ? 32 : 1];
+  __shared__ unsigned long long s_prof[HNUMO_DIAG ? 40 : 1];
   const int e = sa.eperm ? __builtin_amdgcn_readfirstlane(sa.eperm[blockIdx.x]) : (int)blockIdx.x, tid = threadIdx.x;
   const unsigned long long ep = *sa.epoch;
   typedef const __attribute__((address_space(4))) StageArgs CStageArgs;

@@ -32,8 +32,11 @@ for k in range(6):
     if (cur >= prev).all() and (cur <= pr[:, 3]).all():
         print(f"    D{k}        mean {(cur - prev).mean():8.0f} clk")
         prev = cur
-for w in range(4):
-    print(f"    B wave{w} done mean {(pr[:, 12 + w] - pr[:, 1]).mean():8.0f} clk")
+# HNUMO_STAGE_DBG bit 16384 (non-slim persistent bodies): slots 12-15, 6 and 7 carry E in its parts
+esplit = bool(int(os.environ.get("HNUMO_STAGE_DBG", "0")) & 16384) and eng.stage_path == "persistent" and eng.dims["ngl"] < 8
+if not esplit:
+    for w in range(4):
+        print(f"    B wave{w} done mean {(pr[:, 12 + w] - pr[:, 1]).mean():8.0f} clk")
 tot = pr[:, 5] - pr[:, 0]
 print(f"  total per block mean {tot.mean():.0f} clk, max {tot.max():.0f}")
 w0, w1 = pr[:, 30], pr[:, 31]
@@ -79,6 +82,11 @@ if getattr(eng, "stage_path", "") == "persistent" and (pr[:, 26] > 0).all():
     print("  persistent per-stage phase means: A2 %.0f | B %.0f | D %.0f (%s %.0f) | E %.0f clk"
           % (ph[0].mean(), ph[1].mean(), ph[2].mean(), "wave-0 volume sums" if slim else "of E: E2 trace stores",
              ph[4].mean(), ph[3].mean()))
+    if esplit:
+        es = [pr[:, k] / nst for k in (12, 13, 14, 15, 6, 7)]
+        print("  E in its parts, per-stage means: E1 %.0f | gradient (with its barrier) %.0f | wait for the re-fetched "
+              "B inputs, last wave %.0f | barrier in front of E2 %.0f clk; the longest wave's own wait %.0f clk; "
+              "the last D phase %.0f clk" % tuple(x.mean() for x in (es[0], es[1], es[2], es[3], es[5], es[4])))
     rp = None if slim else pr[:, 23] / nst  # share of the stages in which the block polled again
     if (pr[:, 23] > 0).all() and (pr[:, 28] > 0).all():  # SLATE (N=7): the last stage's D split
         print("  last stage, from D's start: volume sums done %.0f clk, the last wave's D work done %.0f clk"
