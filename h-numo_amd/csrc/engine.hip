@@ -32,6 +32,7 @@
 #include "sample_plan.h"
 #include "float_plan.h"
 #include "region_plan.h"
+#include "persist_policy.h"
 #include "kernels_bcl.hip"
 #include "kernels_btp.hip"
 #include "kernels_lapq.hip"
@@ -147,12 +148,7 @@ struct hnumo_engine {
   int occ_blocks[2] = {0, 0}, occ_ncu = 0, probe_ok[2] = {-1, -1};
   int persist_pad = 0;
   int persist_guard = 3;                      // bit 1: occupancy estimate, bit 2: trial launch
-  int persist_aborts = 0;                     // runs that found a persistent launch not co-resident
-  // after an abort the persistent path is suspended, not dropped (maybe_reprobe): per-stage runs
-  // while persist_wait counts down, then a stage-less trial launch decides; the wait doubles with
-  // every abort or failed re-probe (up to 1024 runs) and resets after a completed persistent run
-  bool persist_suspended = false;
-  int persist_wait = 0, persist_backoff = 1, persist_reprobes = 0, persist_recovered = 0;
+  PersistPolicy persist;  // suspended after an abort, not dropped (run_with_redo and maybe_reprobe alone write it)
   unsigned long long *dbg_abort_epoch = nullptr;  // hnumo_debug_force_abort: the launch epoch to abort
   StageArgs *d_stages[2] = {nullptr, nullptr};  // per-stage arguments: predictor (qp), corrector (qp2)
   // processor-face halo: the reference's own partition contract (face(8) = 0 faces listed per
@@ -204,6 +200,7 @@ struct hnumo_engine {
     std::vector<hipEvent_t> ev;
     std::vector<const char *> name;
     size_t n = 0;
+    ~KMarks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
   } *km = nullptr;
   // on-device run diagnostics (kernels_diag.hip).  has_state: q and qb were uploaded at least once;
   // the rest is hnumo_diag_geometry's: the running cell minima of courant.F90:98-99 per sub-cell
@@ -1003,7 +1000,7 @@ static int stage_table(hnumo_engine *e, const double *qp, std::vector<StageArgs>
 // (single rank only: its stage tables send every trace to an element slot)
 static bool use_persistent(const hnumo_engine *e) {
   return e->comm_mode == 0 && e->nranks == 1 && !e->face_halo && !e->lapq_on && e->persistent_ok[e->summation] &&
-         !e->persist_suspended;
+         !e->persist.suspended;
 }
 
 // ti_barotropic_ssprk_mlswe (mod_rk_mlswe.F90:19-151) on device state qb_state
@@ -1406,6 +1403,49 @@ static void fill_devmesh(hnumo_engine *eng, const SetupPlan &pl) {
   m.steps_done = eng->steps_done;
 }
 
+static int transport_error(hnumo_engine *eng) {
+  if (!eng->comm_err.empty()) {
+    std::string m = eng->comm_err;
+    eng->comm_err.clear();
+    return fail(eng, HNUMO_ERR_DEVICE, "halo exchange failed: " + m);
+  }
+  if (eng->group && eng->group->aborted) return fail(eng, HNUMO_ERR_DEVICE, "local exchange group aborted by another engine");
+  return 0;
+}
+
+// what a flagged run leaves: the device flag word (flag_error names its bits), the steps whose corrector completed
+struct RunFlags {
+  int flags = 0, done = 0;
+  bool aborted() const { return flags & RUN_ABORT; }  // a persistent launch of the run was not co-resident
+};
+
+// The one place where the host clears and reads the run's flag word and step counter: clear both,
+// enqueue() the work on the engine stream (around whatever it times with events), copy both back,
+// synchronise, then the HIP and transport errors.  An aborted run's flag word is cleared again at once:
+// the kernels of the entries that never read the flags test RUN_ABORT too.
+template <class Enqueue>
+static int flagged_run(hnumo_engine *eng, Enqueue &&enqueue, RunFlags &out) {
+  HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
+  HIPCHK(hipMemsetAsync(eng->steps_done, 0, sizeof(unsigned), eng->stream));
+  if (int rc = enqueue()) return rc;
+  HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipMemcpyAsync(eng->h_steps, eng->steps_done, sizeof(unsigned), hipMemcpyDeviceToHost, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  HIPCHK(hipGetLastError());
+  out.flags = *eng->h_neg;
+  out.done = (int)*eng->h_steps;
+  if (out.aborted()) HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
+  return transport_error(eng);
+}
+
+// a stage-less trial launch (Launch::probe, the residency rendezvous alone): all workgroups resident at once?
+static int probe_resident(hnumo_engine *eng, int summation, bool &resident) {
+  RunFlags r;
+  const int rc = flagged_run(eng, [&] { DISPATCH(eng, probe(eng, summation)); return 0; }, r);
+  resident = !r.aborted();
+  return rc;
+}
+
 // persistent sub-cycle: its buffers, the occupancy estimate, the placement, the stage tables of the
 // two sub-cycles of a step and the residency trial launches
 static int setup_persistent(hnumo_engine *eng, const SetupPlan &pl, const Knobs &k, int ncu) {
@@ -1439,14 +1479,10 @@ static int setup_persistent(hnumo_engine *eng, const SetupPlan &pl, const Knobs 
     // the trial launches: what the dispatcher does, not what the estimate says, decides
     for (int sm = 0; sm < 2 && (eng->persist_guard & 2); sm++) {
       if (!eng->persistent_ok[sm] || eng->comm_mode != 0 || eng->nranks != 1) continue;
-      HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-      DISPATCH(eng, probe(eng, sm));
-      HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-      HIPCHK(hipStreamSynchronize(eng->stream));
-      HIPCHK(hipGetLastError());
-      eng->probe_ok[sm] = (*eng->h_neg & RUN_ABORT) ? 0 : 1;
-      if (!eng->probe_ok[sm]) eng->persistent_ok[sm] = false;
-      HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
+      bool resident = false;
+      if (int rc = probe_resident(eng, sm, resident)) return rc;
+      eng->probe_ok[sm] = resident ? 1 : 0;
+      if (!resident) eng->persistent_ok[sm] = false;
     }
   }
   return 0;
@@ -1768,7 +1804,7 @@ static int ensure_graph(hnumo_engine *eng) {
 
 // error bits of the device flag word (neg_flag): 1 negative thickness, 2 non-finite
 // state, 8 a persistent sub-cycle trace wait timed out, 16 (RUN_ABORT) a persistent launch found
-// its workgroups not co-resident -- handled by the callers (persistent_abort), never an error
+// its workgroups not co-resident -- handled by run_with_redo, never an error
 static int flag_error(hnumo_engine *eng, int flags) {
   if (flags & 1) return fail(eng, HNUMO_ERR_NEGATIVE_THICKNESS, "Negative mass in thickness at some points");
   if (flags & 2) return fail(eng, HNUMO_ERR_NONFINITE, "non-finite barotropic state");
@@ -1785,55 +1821,44 @@ static void drop_graph(hnumo_engine *eng) {
   if (eng->comm_mode != 1) eng->no_graph = false;
 }
 
-// A persistent launch of the run was not co-resident (RUN_ABORT): it did no work, and neither
-// did anything after it that writes the step state, so the state is that of the last completed
-// step.  The engine suspends the persistent path (maybe_reprobe brings it back once a trial launch
-// finds the grid resident again) and the caller repeats what is left on per-stage launches.
-static void persistent_abort(hnumo_engine *eng) {
-  eng->persist_suspended = true;
-  eng->persist_aborts++;
-  eng->persist_wait = eng->persist_backoff;
-  eng->persist_backoff = std::min(2 * eng->persist_backoff, 1024);
-  drop_graph(eng);
-}
-
-// Before a run: a suspended persistent path whose wait is over gets one stage-less trial launch
-// (Launch::probe, the residency rendezvous alone); all workgroups resident -> persistent again.
+// Before a run (never before the redo of one): a suspended persistent path whose wait is over gets
+// one trial launch; all workgroups resident -> persistent again.
 // (A co-resident job that held CUs for a moment costs a few per-stage runs, not the engine's
 // lifetime on per-stage launches; one that stays costs a 20 ms probe every 1024 runs at most.)
 static int maybe_reprobe(hnumo_engine *eng) {
-  if (!eng->persist_suspended || !eng->persistent_ok[eng->summation]) return 0;
-  if (eng->persist_wait > 0) {
-    eng->persist_wait--;
-    return 0;
-  }
-  eng->persist_reprobes++;
-  HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-  DISPATCH(eng, probe(eng, eng->summation));
-  HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  const bool resident = !(*eng->h_neg & RUN_ABORT);
-  HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-  if (resident) {
-    eng->persist_suspended = false;
-    eng->persist_recovered++;
-    drop_graph(eng);
-  } else {
-    eng->persist_wait = eng->persist_backoff;
-    eng->persist_backoff = std::min(2 * eng->persist_backoff, 1024);
-  }
+  if (!eng->persistent_ok[eng->summation] || !eng->persist.due_for_probe()) return 0;
+  bool resident = false;
+  if (int rc = probe_resident(eng, eng->summation, resident)) return rc;
+  eng->persist.probed(resident);
+  if (resident) drop_graph(eng);
   return 0;
 }
 
-static int transport_error(hnumo_engine *eng) {
-  if (!eng->comm_err.empty()) {
-    std::string m = eng->comm_err;
-    eng->comm_err.clear();
-    return fail(eng, HNUMO_ERR_DEVICE, "halo exchange failed: " + m);
+// what run_with_redo repeats after an abort: the steps that did not complete, or the whole call
+enum class Redo { steps_left, whole };
+
+// The one driver of every entry that launches a step or a sub-cycle: enqueue(n) as a flagged run, its
+// errors reported through flag_error(flags & mask).  A persistent launch of the run that was not
+// co-resident (RUN_ABORT) did no work, and neither did anything after it that writes the step state,
+// so the state is that of the last completed step.  The errors of the steps that completed are
+// reported, not cleared by the redo; the path is suspended (maybe_reprobe brings it back), the captured
+// step dropped, and what is left is enqueued again, now on per-stage launches.  The redo neither
+// re-probes nor counts as a run of the wait the abort just set.
+extern "C++" template <class Enqueue>
+static int run_with_redo(hnumo_engine *eng, int n, Redo redo, int mask, Enqueue &&enqueue) {
+  for (;;) {
+    const bool pers = use_persistent(eng);
+    RunFlags r;
+    if (int rc = flagged_run(eng, [&] { return enqueue(n); }, r)) return rc;
+    const bool aborted = r.aborted();
+    if (aborted && !pers) return fail(eng, HNUMO_ERR_DEVICE, "run aborted off the persistent path");
+    if (!aborted && pers) eng->persist.completed_persistent();
+    if (int rc = flag_error(eng, r.flags & mask)) return rc;
+    if (!aborted) return 0;
+    eng->persist.abort();
+    drop_graph(eng);
+    if (redo == Redo::steps_left && (n -= r.done) <= 0) return 0;
   }
-  if (eng->group && eng->group->aborted) return fail(eng, HNUMO_ERR_DEVICE, "local exchange group aborted by another engine");
-  return 0;
 }
 
 static int launch_steps(hnumo_engine *eng, int nsteps) {
@@ -1848,31 +1873,10 @@ static int launch_steps(hnumo_engine *eng, int nsteps) {
   return 0;
 }
 
-// (retry: the per-stage repeat of a run whose persistent launch gave up -- it does not count as a
-// run of the back-off wait that abort just set)
-static int run_steps(hnumo_engine *eng, int nsteps, bool retry = false) {
-  int rc = retry ? 0 : maybe_reprobe(eng);
-  if (rc) return rc;
-  const bool pers = use_persistent(eng);
-  HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-  HIPCHK(hipMemsetAsync(eng->steps_done, 0, sizeof(unsigned), eng->stream));
-  rc = launch_steps(eng, nsteps);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipMemcpyAsync(eng->h_steps, eng->steps_done, sizeof(unsigned), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  if ((rc = transport_error(eng))) return rc;
-  if ((*eng->h_neg & RUN_ABORT) && !use_persistent(eng)) return fail(eng, HNUMO_ERR_DEVICE, "run aborted off the persistent path");
-  if (*eng->h_neg & RUN_ABORT) {
-    const int done = (int)*eng->h_steps;
-    // an error of a step that completed before the abort is reported, not cleared by the retry
-    if ((rc = flag_error(eng, *eng->h_neg & ~RUN_ABORT))) return rc;
-    persistent_abort(eng);
-    return done < nsteps ? run_steps(eng, nsteps - done, true) : 0;
-  }
-  if (pers) eng->persist_backoff = 1;  // a completed persistent run
-  return flag_error(eng, *eng->h_neg);
+// (after an abort the steps that completed stand and the rest are redone: run_with_redo)
+static int run_steps(hnumo_engine *eng, int nsteps) {
+  if (int rc = maybe_reprobe(eng)) return rc;
+  return run_with_redo(eng, nsteps, Redo::steps_left, ~0, [&](int left) { return launch_steps(eng, left); });
 }
 
 // A multi-rank engine exchanges halos inside these calls: it needs its RCCL transport (a local
@@ -1954,16 +1958,14 @@ int hnumo_persistent_info(hnumo_engine *eng, int32_t *out) {
   }
   (void)hipGetLastError();
   const int32_t v[8] = {use_persistent(eng) ? 1 : 0, eng->occ_blocks[0], eng->occ_blocks[1], eng->occ_ncu,
-                        eng->probe_ok[0], eng->probe_ok[1], eng->persist_aborts, lds};
+                        eng->probe_ok[0], eng->probe_ok[1], eng->persist.aborts, lds};
   std::memcpy(out, v, sizeof(v));
   return 0;
 }
 
 int hnumo_persistent_stats(hnumo_engine *eng, int32_t *out4) {
   if (!eng || !out4) return HNUMO_ERR_INVALID;
-  const int32_t v[4] = {eng->persist_aborts, eng->persist_reprobes, eng->persist_recovered,
-                        eng->persist_suspended ? eng->persist_wait : -1};
-  std::memcpy(out4, v, sizeof(v));
+  eng->persist.stats(out4);
   return 0;
 }
 
@@ -2166,18 +2168,9 @@ int hnumo_ti_barotropic_ssprk(hnumo_engine *eng, double *qb_df, const double *qp
   rc = upload_state(eng, nullptr, qb_df, qprime_df);
   if (rc) return rc;
   if ((rc = maybe_reprobe(eng))) return rc;
-  for (;;) {
-    HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-    launch_subcycle(eng, eng->qbp, eng->qp);
-    HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-    HIPCHK(hipStreamSynchronize(eng->stream));
-    HIPCHK(hipGetLastError());
-    if ((rc = transport_error(eng))) return rc;
-    if (!(*eng->h_neg & RUN_ABORT) || !use_persistent(eng)) break;
-    persistent_abort(eng);  // (the launch did no work: qb is still the input)
-  }
-  if (use_persistent(eng)) eng->persist_backoff = 1;  // a completed persistent run
-  if ((rc = flag_error(eng, *eng->h_neg & ~RUN_ABORT))) return rc;
+  // (an aborted launch did no work, qb is still the input: the redo is the whole sub-cycle)
+  rc = run_with_redo(eng, 1, Redo::whole, ~0, [&](int) { launch_subcycle(eng, eng->qbp, eng->qp); return 0; });
+  if (rc) return rc;
   launch_copy(eng, eng->qb, eng->qbp, 4 * (size_t)eng->npoin);
   return download_state(eng, nullptr, qb_df, nullptr);
 }
@@ -2190,18 +2183,9 @@ int hnumo_predict(hnumo_engine *eng, double *q_df, double *qb_df, double *qprime
   rc = upload_state(eng, q_df, qb_df, qprime_df);
   if (rc) return rc;
   if ((rc = maybe_reprobe(eng))) return rc;
-  for (;;) {
-    HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-    launch_predict(eng);
-    HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-    HIPCHK(hipStreamSynchronize(eng->stream));
-    HIPCHK(hipGetLastError());
-    if ((rc = transport_error(eng))) return rc;
-    if (!(*eng->h_neg & RUN_ABORT) || !use_persistent(eng)) break;
-    persistent_abort(eng);  // (the predictor writes only q_df2, qbp, qprime_df2: redo it)
-  }
-  if (use_persistent(eng)) eng->persist_backoff = 1;  // a completed persistent run
-  if ((rc = flag_error(eng, *eng->h_neg & ~RUN_ABORT))) return rc;
+  // (the predictor writes only q_df2, qbp, qprime_df2: the redo after an abort is the whole of it)
+  rc = run_with_redo(eng, 1, Redo::whole, ~0, [&](int) { launch_predict(eng); return 0; });
+  if (rc) return rc;
   const size_t n3 = 3 * (size_t)eng->npoin * eng->L;
   HIPCHK(hipMemcpyAsync(q_df, eng->q2, n3 * 8, hipMemcpyDeviceToHost, eng->stream));
   HIPCHK(hipMemcpyAsync(qb_df, eng->qbp, 4 * (size_t)eng->npoin * 8, hipMemcpyDeviceToHost, eng->stream));
@@ -2379,24 +2363,16 @@ int hnumo_bench_steps(hnumo_engine *eng, int nsteps, double *ms_total, double *m
   HIPCHK(hipSetDevice(eng->device));
   int rc = maybe_reprobe(eng);
   if (rc) return rc;
-  if ((rc = ensure_graph(eng))) return rc;
-  HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-  HIPCHK(hipEventRecord(eng->ev0, eng->stream));
-  rc = launch_steps(eng, nsteps);
+  // a timed run whose state went bad (or whose persistent hand-offs timed out) is no result; one whose
+  // persistent launch gave up is timed again, whole (the steps that completed stand all the same)
+  rc = run_with_redo(eng, nsteps, Redo::whole, ~0, [&](int n) -> int {
+    if (int r = ensure_graph(eng)) return r;  // (a capture stays outside the timed region)
+    HIPCHK(hipEventRecord(eng->ev0, eng->stream));
+    if (int r = launch_steps(eng, n)) return r;
+    HIPCHK(hipEventRecord(eng->ev1, eng->stream));
+    return 0;
+  });
   if (rc) return rc;
-  HIPCHK(hipEventRecord(eng->ev1, eng->stream));
-  HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipEventSynchronize(eng->ev1));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  // a timed run whose state went bad (or whose persistent hand-offs timed out) is no result
-  if ((rc = transport_error(eng))) return rc;
-  if ((*eng->h_neg & RUN_ABORT) && use_persistent(eng)) {
-    // (not co-resident: drop the persistent path and time the run again on per-stage launches)
-    persistent_abort(eng);
-    return hnumo_bench_steps(eng, nsteps, ms_total, ms_kernel_avg, kernel_launches);
-  }
-  if ((rc = flag_error(eng, *eng->h_neg))) return rc;
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, eng->ev0, eng->ev1));
   if (ms_total) *ms_total = ms;
@@ -2421,28 +2397,22 @@ int hnumo_time_stage_kernel(hnumo_engine *eng, int nsubcycles, double *ms_kernel
   }
   (void)hipGetLastError();  // clear a sticky error left by an unsupported in-graph event record
   // the corrector sub-cycle of the current device state, on a scratch copy of qb
-  const bool ke = eng->kernel_events;
-  eng->kernel_events = true;
-  HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
+  // (mask 8: a timed-out trace wait alone voids the timing; after an abort every sub-cycle is timed again)
   double total = 0.0;
-  for (int s = 0; s < nsubcycles; s++) {
-    launch_subcycle(eng, eng->qbp, eng->qp, true);
-    HIPCHK(hipEventSynchronize(eng->evk1));
-    float mk = 0.f;
-    HIPCHK(hipEventElapsedTime(&mk, eng->evk0, eng->evk1));
-    total += mk;
-  }
-  eng->kernel_events = ke;
-  HIPCHK(hipMemcpyAsync(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  HIPCHK(hipGetLastError());
-  if ((*eng->h_neg & RUN_ABORT) && use_persistent(eng)) {
-    persistent_abort(eng);
-    HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-    return hnumo_time_stage_kernel(eng, nsubcycles, ms_kernel_avg);
-  }
-  int rc = transport_error(eng);
-  if (!rc) rc = flag_error(eng, *eng->h_neg & 8);
+  const int rc = run_with_redo(eng, nsubcycles, Redo::whole, 8, [&](int n) -> int {
+    const bool ke = eng->kernel_events;
+    eng->kernel_events = true;
+    total = 0.0;
+    for (int s = 0; s < n; s++) {
+      launch_subcycle(eng, eng->qbp, eng->qp, true);
+      HIPCHK(hipEventSynchronize(eng->evk1));
+      float mk = 0.f;
+      HIPCHK(hipEventElapsedTime(&mk, eng->evk0, eng->evk1));
+      total += mk;
+    }
+    eng->kernel_events = ke;
+    return 0;
+  });
   if (rc) return rc;
   *ms_kernel_avg = total / ((double)nsubcycles * eng->p.N_btp * eng->K);
   return 0;
@@ -2558,54 +2528,36 @@ int hnumo_group_floats_advance(hnumo_engine **engines, int n, int32_t id, double
 // Per-kernel breakdown of a step: `nsteps` direct (uncaptured) steps of the resident device state
 // with an event after every launch on the engine stream; the span between two marks is charged to
 // the kernel family of the later one.  Single-stream engines (one rank) only.
-// (retry: the per-stage repeat of the steps a persistent launch that gave up left undone, as in
-// run_steps: it neither re-probes nor counts as a run of the back-off wait)
-static int step_breakdown(hnumo_engine *eng, int nsteps, char *names, int64_t names_len, double *us_per_step,
-                          int max_kernels, int *count, bool retry) {
+int hnumo_step_breakdown(hnumo_engine *eng, int nsteps, char *names, int64_t names_len, double *us_per_step,
+                         int max_kernels, int *count) {
+  if (!eng || nsteps < 1 || !names || names_len < 1 || !us_per_step || max_kernels < 1 || !count)
+    return HNUMO_ERR_INVALID;
   if (eng->comm_mode != 0 || eng->nranks != 1 || eng->face_halo)
     return fail(eng, HNUMO_ERR_INVALID, "step breakdown: single-rank engines only");
   if (!eng->resident || !eng->uploaded)
     return fail(eng, HNUMO_ERR_INVALID, "step breakdown: needs a resident, uploaded state (hnumo_set_resident)");
   HIPCHK(hipSetDevice(eng->device));
-  int rc = retry ? 0 : maybe_reprobe(eng);
+  int rc = maybe_reprobe(eng);
   if (rc) return rc;
-  hnumo_engine::KMarks km;
-  HIPCHK(hipMemsetAsync(eng->neg_flag, 0, sizeof(int), eng->stream));
-  HIPCHK(hipMemsetAsync(eng->steps_done, 0, sizeof(unsigned), eng->stream));
-  eng->km = &km;
-  kmark(eng, "start");
-  for (int s = 0; s < nsteps; s++) launch_step(eng);
-  eng->km = nullptr;
-  auto release = [&]() {
-    for (hipEvent_t ev : km.ev) (void)hipEventDestroy(ev);
-  };
-  if (hipStreamSynchronize(eng->stream) != hipSuccess ||
-      hipMemcpy(eng->h_neg, eng->neg_flag, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(eng->h_steps, eng->steps_done, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) {
-    release();
-    return fail(eng, HNUMO_ERR_DEVICE, "step breakdown: HIP error");
-  }
-  if ((*eng->h_neg & RUN_ABORT) && use_persistent(eng)) {
-    // the steps completed before the abort stand (their errors are reported); the rest are redone
-    // and timed on per-stage launches, so the state advances by exactly nsteps
-    release();
-    const int done = (int)*eng->h_steps;
-    if ((rc = flag_error(eng, *eng->h_neg & ~RUN_ABORT))) return rc;
-    persistent_abort(eng);
-    return step_breakdown(eng, nsteps - done, names, names_len, us_per_step, max_kernels, count, true);
-  }
-  if ((rc = flag_error(eng, *eng->h_neg))) {
-    release();
-    return rc;
-  }
+  hnumo_engine::KMarks km;  // (its events are destroyed with it)
+  // the steps completed before an abort stand (their errors are reported); the rest are redone and
+  // timed on per-stage launches (the marks start over), so the state advances by exactly nsteps
+  rc = run_with_redo(eng, nsteps, Redo::steps_left, ~0, [&](int left) {
+    nsteps = left;  // (what the marks below cover: us_per_step divides by it)
+    km.n = 0;
+    eng->km = &km;
+    kmark(eng, "start");
+    for (int s = 0; s < left; s++) launch_step(eng);
+    eng->km = nullptr;
+    return 0;
+  });
+  if (rc) return rc;
   std::vector<std::string> nm;
   std::vector<double> ms;
   for (size_t i = 1; i < km.n; i++) {
     float dt = 0.f;
-    if (hipEventElapsedTime(&dt, km.ev[i - 1], km.ev[i]) != hipSuccess) {
-      release();
+    if (hipEventElapsedTime(&dt, km.ev[i - 1], km.ev[i]) != hipSuccess)
       return fail(eng, HNUMO_ERR_DEVICE, "step breakdown: event timing failed");
-    }
     size_t j = 0;
     while (j < nm.size() && nm[j] != km.name[i]) j++;
     if (j == nm.size()) {
@@ -2614,7 +2566,6 @@ static int step_breakdown(hnumo_engine *eng, int nsteps, char *names, int64_t na
     }
     ms[j] += dt;
   }
-  release();
   std::string joined;
   const int nk = std::min<int>((int)nm.size(), max_kernels);
   for (int j = 0; j < nk; j++) {
@@ -2625,13 +2576,6 @@ static int step_breakdown(hnumo_engine *eng, int nsteps, char *names, int64_t na
   std::memcpy(names, joined.c_str(), joined.size() + 1);
   *count = nk;
   return 0;
-}
-
-int hnumo_step_breakdown(hnumo_engine *eng, int nsteps, char *names, int64_t names_len, double *us_per_step,
-                         int max_kernels, int *count) {
-  if (!eng || nsteps < 1 || !names || names_len < 1 || !us_per_step || max_kernels < 1 || !count)
-    return HNUMO_ERR_INVALID;
-  return step_breakdown(eng, nsteps, names, names_len, us_per_step, max_kernels, count, false);
 }
 
 }  // extern "C"

@@ -154,6 +154,98 @@ def test_corrector_abort_is_redone_and_path_recovers(case_factory, monkeypatch):
     e0.close()
 
 
+def small_pair(case_factory, monkeypatch):
+    """(case, persistent engine, oracle engine on per-stage launches from its creation) of the smallest case of
+    the observer tests: bump10 at N = 2 (100 elements, 2 layers) carrying tests/states.py's moving state."""
+    import float_cases as FC
+    from hnumo.engine import Engine
+    case = FC.moving(case_factory, "bump10", {"nop": 2})
+    e = Engine(case)
+    assert e.stage_path == "persistent", e.persistent_info
+    monkeypatch.setenv("HNUMO_PERSISTENT", "0")
+    e0 = Engine(case)
+    monkeypatch.delenv("HNUMO_PERSISTENT")
+    assert e0.stage_path == "per-stage"
+    return case, e, e0
+
+
+def test_predict_abort_redoes_the_whole_predictor(case_factory, monkeypatch):
+    """hnumo_predict whose sub-cycle launch gives up: the aborted launch wrote nothing the call returns, the
+    whole predictor is redone on per-stage launches -- the per-stage engine's three outputs bit for bit."""
+    _, e, e0 = small_pair(case_factory, monkeypatch)
+    e.debug_force_abort(0)
+    a, b = e.state(), e0.state()
+    e.predict(*a)
+    e0.predict(*b)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    assert e.persistent_stats["aborts"] == 1 and e.stage_path == "per-stage", e.persistent_stats
+    e.close()
+    e0.close()
+
+
+def test_barotropic_ssprk_abort_redoes_the_whole_subcycle(case_factory, monkeypatch):
+    """hnumo_ti_barotropic_ssprk whose launch gives up: qb_df is the per-stage engine's bit for bit."""
+    _, e, e0 = small_pair(case_factory, monkeypatch)
+    e.debug_force_abort(0)
+    (_, qa, pa), (_, qb, pb) = e.state(), e0.state()
+    e.ti_barotropic_ssprk(qa, pa)
+    e0.ti_barotropic_ssprk(qb, pb)
+    assert np.array_equal(qa, qb) and np.array_equal(pa, pb)
+    assert e.persistent_stats["aborts"] == 1 and e.stage_path == "per-stage", e.persistent_stats
+    e.close()
+    e0.close()
+
+
+def test_bench_steps_abort_times_the_run_again_without_spending_the_wait(case_factory, monkeypatch):
+    """hnumo_bench_steps(2) on a resident engine whose second step's corrector launch gives up (launch 3 from
+    now, after one ti_rk_bcl).  The first timed step stands and the whole run of 2 is timed again on per-stage
+    launches: the state is that of 4 steps of the per-stage engine (1 ti_rk_bcl + 1 that stood + 2 timed again;
+    measured on the parent of the change that introduced run_with_redo: 4).  The redo neither re-probes nor
+    spends the run of the wait the abort set: wait == 1 (that parent, re-entering through its own top, left 0)."""
+    _, e, e0 = small_pair(case_factory, monkeypatch)
+    e.set_resident(True)
+    a, b = e.state(), e0.state()
+    e.ti_rk_bcl(*a)
+    e.debug_force_abort(3)
+    ms_total, _, launches = e.bench_steps(2)
+    assert ms_total > 0 and launches > 0
+    st = e.persistent_stats
+    print("bench_steps after an abort: persistent_stats", st)
+    assert st["aborts"] == 1 and st["reprobes"] == 0, st
+    e.sync(*a)
+    for _ in range(4):
+        e0.ti_rk_bcl(*b)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    assert st["wait"] == 1, st
+    e.close()
+    e0.close()
+
+
+def test_time_stage_kernel_abort_times_again_and_leaves_the_state(case_factory, monkeypatch):
+    """hnumo_time_stage_kernel(2) whose second sub-cycle launch gives up: both are timed again on per-stage
+    launches, a positive time comes back, and the device state is untouched (the sub-cycles write to scratch):
+    the resident engine's next step has the per-stage engine's bits."""
+    _, e, e0 = small_pair(case_factory, monkeypatch)
+    e.set_resident(True)
+    e0.set_resident(True)
+    a, b = e.state(), e0.state()
+    e.ti_rk_bcl(*a)
+    e0.ti_rk_bcl(*b)
+    e.debug_force_abort(1)
+    assert e.time_stage_kernel(2) > 0
+    assert e.persistent_stats["aborts"] == 1 and e.stage_path == "per-stage", e.persistent_stats
+    e.ti_rk_bcl(*a)
+    e0.ti_rk_bcl(*b)
+    e.sync(*a)
+    e0.sync(*b)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    e.close()
+    e0.close()
+
+
 def test_predict_on_resident_engine_reuploads(case_factory):
     """hnumo_predict replaces the device state with the caller's input (ABI v7): a resident
     engine's next step then starts from the caller's arrays, not from its old device state."""
