@@ -212,7 +212,9 @@ struct hnumo_engine {
   const double *diag_w = nullptr;
   double *h_diag = nullptr;                  // pinned copy of diag_out
   double diag_min_dx = 1e16, diag_min_dy = 1e16;
-  // the observers of the resident state (observers.hip), each with the Series it records into.
+  // the observers of the resident state (observers.hip).  Each of the four field observers has `on` (between
+  // its begin and its end), its buffers, which its X_free frees and resets, and a Series: the ring it records
+  // into, and with capacity 0 still the `every` and the steps that say when a sample is due after a step.
   // online flow statistics (hnumo_stats_begin .. hnumo_stats_end): the running sums, the samples taken
   struct Stats {
     bool on = false;
@@ -230,14 +232,15 @@ struct hnumo_engine {
     Series series;
   } vort;
   // eddy covariances (hnumo_cov_begin .. hnumo_cov_end; kernels_cov.hip): the caller's coriolis_df and
-  // zref (NULL: 0), the running sums [L][7][npoin] pairs, the samples taken, `every` and the steps
-  // counted for it, the element partials [3L][ne] with their tree and the integrals [3L]
+  // zref (NULL: 0), the running sums [L][7][npoin] pairs, the samples taken, the element partials [3L][ne]
+  // with their tree and the integrals [3L]; the series is begun with capacity 0: it holds `every` and the
+  // steps counted for it, no ring
   struct Cov {
     bool on = false;
     double *f = nullptr, *zref = nullptr, *sums = nullptr, *integ = nullptr;
-    int64_t nsamples = 0, steps = 0;
-    int every = 0;
+    int64_t nsamples = 0;
     TreeSum tree;
+    Series series;
   } cov;
   // energy budget (hnumo_energy_begin .. hnumo_energy_end; kernels_energy.hip): the caller's zref (NULL:
   // 0), the running sums (S_W, S_D) [npoin_q] pairs and S_V [L][npoin], the samples taken, the element

@@ -8,11 +8,56 @@
 // (with Series and TreeSum) are defined.  All of it is plain launches on the engine stream outside
 // the captured step: the step's launches, graph and bits are the same with or without observers.
 //
-// An observer is a kernel, a Series, an entry in observers_after_step and a free in
-// hnumo_engine_destroy; the pieces below are what the seven have in common (the eddy covariances keep
-// no series: their `every` stands alone).
+// An observer writes: its kernel; its state in hnumo_engine with a Series (capacity 0 where it keeps none:
+// `every` then stands alone and counts in series.steps all the same); X_free, called by hnumo_engine_destroy
+// too; a begin that refuses its own arguments, then drain_and_free, its allocations (alloc_doubles,
+// upload_optional, tree_alloc, series_begin) or begin_failed; an end through observer_end; a sample that
+// launches on the engine stream; an arm of observers_after_step on series_due.  It gets from the pieces
+// below: the refusals of its entry points with their texts and their precedence (no_engine, not_begun,
+// null_arg, wrong_n, no_samples, no_state; set_by_id for the sets), the ring and its read (series_*), the
+// tree sum, the paired sums' two layouts (sums_read, sums_write), the fields of such sums (fields_of_sums)
+// and, from observer_layout.h, the index work of those and the launch grids, which run on the CPU too.
+#include "observer_layout.h"
 
 // ------------------------------------------------------------------ shared pieces
+// ---- the way in.  Each states one refusal and is true when it refuses, with the message set.  An entry
+// chains those that apply with || and returns HNUMO_ERR_INVALID; the order in the chain is which one wins --
+// not begun, a NULL argument, a wrong n, no samples -- and the chain stands ahead of the entry's first HIP
+// call wherever no refusal depends on the device (a broken device does not mask an argument error)
+static bool no_engine(const hnumo_engine *eng) { return !eng; }
+
+static bool refused(hnumo_engine *eng, const char *who, const std::string &why) {
+  return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": " + why) != 0;
+}
+
+static bool not_begun(hnumo_engine *eng, bool on, const char *who, const char *begin) {
+  return !on && refused(eng, who, std::string("call ") + begin + " first");
+}
+
+static bool null_arg(hnumo_engine *eng, const void *p, const char *who, const char *name) {
+  return !p && refused(eng, who, std::string(name) + " is NULL");
+}
+
+// `shape`: what `name` counts, in the caller's words
+static bool wrong_n(hnumo_engine *eng, int64_t n, int64_t want, const char *who, const char *shape, const char *name = "n") {
+  return n != want && refused(eng, who, std::string(name) + " must be " + shape + " = " + std::to_string(want) + ", got " + std::to_string(n));
+}
+
+static bool wrong_M(hnumo_engine *eng, int64_t M, int64_t want, const char *who) {
+  return M != want && refused(eng, who, "M must be the set's " + std::to_string(want) + ", got " + std::to_string(M));
+}
+
+// a begin's two counts, `names` in the caller's words
+static bool negative(hnumo_engine *eng, int a, int b, const char *who, const char *names) {
+  return (a < 0 || b < 0) && refused(eng, who, std::string(names) + " must be >= 0, got " + std::to_string(a) + ", " + std::to_string(b));
+}
+
+static bool no_samples(hnumo_engine *eng, int64_t nsamples, const char *who) { return nsamples == 0 && refused(eng, who, "no samples yet"); }
+
+static bool no_state(hnumo_engine *eng, const char *who) {
+  return !eng->has_state && refused(eng, who, "no state on the device yet (run a step first)");
+}
+
 // eng->L and eng->ngl as compile-time constants for a generic lambda (unsupported values are
 // refused before any launch; the default arms are never taken for them)
 template <class F>
@@ -53,14 +98,45 @@ static void dfree(T *&...p) {
   ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
 }
 
-// the set `id` of sets[], or nullptr with the message set; the first unused slot of sets[], or -1
+// the engine's device current and its stream drained: ahead of freeing or rewriting what a launch in flight uses
+static int drain(hnumo_engine *eng) {
+  HIPCHK(hipSetDevice(eng->device));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  return HNUMO_OK;
+}
+
+// ---- begin and end of a field observer, whose X_free frees its buffers and resets its state
+// what a begin and an end start with (a sample in flight uses the old buffers)
+static int drain_and_free(hnumo_engine *eng, void (*free_state)(hnumo_engine *)) {
+  if (int rc = drain(eng)) return rc;
+  free_state(eng);
+  return HNUMO_OK;
+}
+
+// a copy of the caller's optional host[n] on the device (NULL: none, *d stays NULL); false: it failed
+static bool upload_optional(double **d, const double *host, size_t n) {
+  return !host || (alloc_doubles(d, n) && hipMemcpy(*d, host, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess);
+}
+
+// a begin whose allocations or uploads failed: nothing of it is left
+static int begin_failed(hnumo_engine *eng, void (*free_state)(hnumo_engine *), const char *msg) {
+  (void)hipGetLastError();
+  free_state(eng);
+  return fail(eng, HNUMO_ERR_DEVICE, msg);
+}
+
+// hnumo_X_end: a no-op before hnumo_X_begin
+static int observer_end(hnumo_engine *eng, bool on, void (*free_state)(hnumo_engine *)) {
+  return on ? drain_and_free(eng, free_state) : HNUMO_OK;
+}
+
+// the set `id` of sets[], or nullptr with the message set (the sets' X_set wrappers answer nullptr for no
+// engine too); the first unused slot of sets[], or -1
 template <class Set, int N>
 static Set *set_by_id(hnumo_engine *eng, Set (&sets)[N], int32_t id, const char *who, const char *kind) {
-  if (id < 0 || id >= N || !sets[id].used) {
-    fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no " + kind + " set with id " + std::to_string(id));
-    return nullptr;
-  }
-  return &sets[id];
+  if (id >= 0 && id < N && sets[id].used) return &sets[id];
+  refused(eng, who, std::string("no ") + kind + " set with id " + std::to_string(id));
+  return nullptr;
 }
 
 template <class Set, int N>
@@ -105,16 +181,6 @@ static int series_full(hnumo_engine *eng, const Series &s, const char *who, cons
   if (s.count < s.cap) return 0;
   return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": " + which + " is full (" + std::to_string(s.cap) + " " + entries +
                                           "): nothing " + done + "; read it with clear = 1");
-}
-
-// planar [V][M] entries -> the caller's (V,M[,count])
-static void sample_transpose(const double *raw, int V, size_t M, size_t count, double *out) {
-  for (size_t c = 0; c < count; c++)
-    for (int v = 0; v < V; v++) {
-      const double *r = raw + (c * V + v) * M;
-      double *o = out + c * V * M + v;
-      for (size_t m = 0; m < M; m++) o[m * V] = r[m];
-    }
 }
 
 // the entries held into `out` (NULL: the count alone), as they are (V = 0) or each from planar [V][M]
@@ -163,6 +229,48 @@ static void tree_sum(hnumo_engine *eng, const TreeSum &t, int rows, int ne, doub
   }
 }
 
+// ---- paired running sums (statistics: NP = 2, covariances: NP = CV_NPAIR) between the device's
+// [L][NP][npoin][2] and the caller's (2*NP,npoin,L); `shape`: that size in the caller's words
+static int sums_read(hnumo_engine *eng, bool on, const double *sums, int NP, double *out, int64_t n, const char *who,
+                     const char *begin, const char *shape) {
+  const size_t want = 2 * (size_t)NP * eng->npoin * eng->L;
+  if (not_begun(eng, on, who, begin) || null_arg(eng, out, who, "out") || wrong_n(eng, n, (int64_t)want, who, shape))
+    return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  if (int rc = download(eng, raw.data(), sums, want * sizeof(double))) return rc;
+  pairs_unpack(raw.data(), NP, eng->L, (size_t)eng->npoin, out);
+  return HNUMO_OK;
+}
+
+static int sums_write(hnumo_engine *eng, bool on, double *sums, int NP, const double *in, int64_t n, int64_t nsamples,
+                      const char *who, const char *begin, const char *shape) {
+  const size_t want = 2 * (size_t)NP * eng->npoin * eng->L;
+  if (not_begun(eng, on, who, begin) || null_arg(eng, in, who, "in") || wrong_n(eng, n, (int64_t)want, who, shape) ||
+      (nsamples < 0 && refused(eng, who, "nsamples must be >= 0")))
+    return HNUMO_ERR_INVALID;
+  HIPCHK(hipSetDevice(eng->device));
+  std::vector<double> raw(want);
+  pairs_pack(in, NP, eng->L, (size_t)eng->npoin, raw.data());
+  HIPCHK(hipMemcpyAsync(sums, raw.data(), want * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+  HIPCHK(hipStreamSynchronize(eng->stream));
+  return HNUMO_OK;
+}
+
+// the fields derived from such sums, `want` doubles into `out`: scratch on the device, the observer's
+// launch(workgroups of `bs` lanes over the nodes, npoin, owned nodes, scratch), the copy back
+template <class Launch>
+static int fields_of_sums(hnumo_engine *eng, int64_t want, int bs, double *out, Launch &&launch) {
+  HIPCHK(hipSetDevice(eng->device));
+  double *d = nullptr;
+  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
+  const size_t npoin = (size_t)eng->npoin;
+  launch(block_count(npoin, bs, 4096), npoin, (size_t)eng->nelem_owned * eng->P, d);
+  const int rc = download(eng, out, d, (size_t)want * sizeof(double));
+  (void)hipFree(d);
+  return rc;
+}
+
 // ------------------------------------------------------------------ online flow statistics
 // eng->stats: the running sums [L][2][npoin] pairs, the element partials [2L][ne] and their tree, the
 // series [capacity][L][2]; nsamples: samples taken since begin
@@ -178,42 +286,29 @@ static void stats_free(hnumo_engine *eng) {
 static size_t stats_nsums(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
 
 extern "C" int hnumo_stats_begin(hnumo_engine *eng, int32_t every, int32_t series_capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (every < 0 || series_capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: every and series_capacity must be >= 0, got " +
-                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  const char *who = "hnumo_stats_begin";
+  if (no_engine(eng) || negative(eng, every, series_capacity, who, "every and series_capacity")) return HNUMO_ERR_INVALID;
   if (eng->L < 1 || eng->L > MAXL || eng->ngl < 2 || eng->ngl * eng->ngl > ST_BS)
     return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_begin: unsupported nlayers or ngl");
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
-  stats_free(eng);
+  if (int rc = drain_and_free(eng, stats_free)) return rc;
   auto &st = eng->stats;
   const int rows = 2 * eng->L;
   if (!alloc_doubles(&st.sums, stats_nsums(eng)) || (series_capacity > 0 && !tree_alloc(st.tree, rows, eng->nelem_owned)) ||
-      series_begin(eng, st.series, rows, every, series_capacity, true) != hipSuccess) {
-    stats_free(eng);
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_stats_begin: device allocation failed");
-  }
+      series_begin(eng, st.series, rows, every, series_capacity, true) != hipSuccess)
+    return begin_failed(eng, stats_free, "hnumo_stats_begin: device allocation failed");
   HIPCHK(hipMemsetAsync(st.sums, 0, stats_nsums(eng) * sizeof(double), eng->stream));
   st.on = true;
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_stats_end(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats.on) return HNUMO_OK;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  stats_free(eng);
-  return HNUMO_OK;
+  return no_engine(eng) ? HNUMO_ERR_INVALID : observer_end(eng, eng->stats.on, stats_free);
 }
 
 // one sample of the state on the device, ordered after what is on the engine stream; no copy back
 static int stats_sample(hnumo_engine *eng, const char *who) {
   auto &st = eng->stats;
-  if (!st.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_stats_begin first");
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (not_begun(eng, st.on, who, "hnumo_stats_begin") || no_state(eng, who)) return HNUMO_ERR_INVALID;
   const bool series = st.series.cap > 0;
   if (series)
     if (int rc = series_full(eng, st.series, who, "the series", "samples", "accumulated")) return rc;
@@ -229,7 +324,7 @@ static int stats_sample(hnumo_engine *eng, const char *who) {
     a.npoin = eng->npoin;
     a.ne = ne;
     a.ngl = eng->ngl;
-    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    const int nb = block_count(ne, EPB);
     with_L(eng->L, [&](auto l) {
       constexpr int L = decltype(l)::value;
       if (series)
@@ -246,80 +341,48 @@ static int stats_sample(hnumo_engine *eng, const char *who) {
 }
 
 extern "C" int hnumo_stats_accumulate(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   return stats_sample(eng, "hnumo_stats_accumulate");
 }
 
-// the sums between the device layout [L][2][npoin][2] and the caller's (4,npoin,L)
 extern "C" int hnumo_stats_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: call hnumo_stats_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: out is NULL");
-  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
-  HIPCHK(hipSetDevice(eng->device));
-  std::vector<double> raw(want);
-  if (int rc = download(eng, raw.data(), eng->stats.sums, want * sizeof(double))) return rc;
-  for (int k = 0; k < eng->L; k++)
-    for (int p = 0; p < 2; p++)
-      for (size_t I = 0; I < npoin; I++)
-        for (int j = 0; j < 2; j++) out[4 * (I + npoin * k) + 2 * p + j] = raw[2 * st_pair(k, p, I, npoin) + j];
-  if (nsamples) *nsamples = eng->stats.nsamples;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
+  const auto &st = eng->stats;
+  if (int rc = sums_read(eng, st.on, st.sums, 2, out, n, "hnumo_stats_sums", "hnumo_stats_begin", "4*npoin*nlayers")) return rc;
+  if (nsamples) *nsamples = st.nsamples;
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_stats_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: call hnumo_stats_begin first");
-  if (!in) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: in is NULL");
-  const size_t want = stats_nsums(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: n must be 4*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
-  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_set_sums: nsamples must be >= 0");
-  HIPCHK(hipSetDevice(eng->device));
-  std::vector<double> raw(want);
-  for (int k = 0; k < eng->L; k++)
-    for (int p = 0; p < 2; p++)
-      for (size_t I = 0; I < npoin; I++)
-        for (int j = 0; j < 2; j++) raw[2 * st_pair(k, p, I, npoin) + j] = in[4 * (I + npoin * k) + 2 * p + j];
-  HIPCHK(hipMemcpyAsync(eng->stats.sums, raw.data(), want * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  eng->stats.nsamples = nsamples;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
+  auto &st = eng->stats;
+  if (int rc = sums_write(eng, st.on, st.sums, 2, in, n, nsamples, "hnumo_stats_set_sums", "hnumo_stats_begin", "4*npoin*nlayers"))
+    return rc;
+  st.nsamples = nsamples;
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_stats_fields(hnumo_engine *eng, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: call hnumo_stats_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: out is NULL");
+  const char *who = "hnumo_stats_fields";
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
+  const auto &st = eng->stats;
   const int64_t want = 5 * (int64_t)eng->npoin * eng->L;
-  if (n != want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: n must be 5*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
-  if (eng->stats.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_fields: no samples yet");
-  HIPCHK(hipSetDevice(eng->device));
-  double *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
-  const size_t npoin = (size_t)eng->npoin, nown = (size_t)eng->nelem_owned * eng->P;
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((npoin + ST_BS - 1) / ST_BS, 4096));
-  const double2 *s = (const double2 *)eng->stats.sums;
-  const double ns = (double)eng->stats.nsamples;
-  with_L(eng->L, [&](auto l) {
-    hipLaunchKernelGGL(stats_fields_kernel<decltype(l)::value>, dim3(nb), dim3(ST_BS), 0, eng->stream, s, npoin, nown, ns, d);
+  if (not_begun(eng, st.on, who, "hnumo_stats_begin") || null_arg(eng, out, who, "out") ||
+      wrong_n(eng, n, want, who, "5*npoin*nlayers") || no_samples(eng, st.nsamples, who))
+    return HNUMO_ERR_INVALID;
+  return fields_of_sums(eng, want, ST_BS, out, [&](int nb, size_t npoin, size_t nown, double *d) {
+    with_L(eng->L, [&](auto l) {
+      hipLaunchKernelGGL(stats_fields_kernel<decltype(l)::value>, dim3(nb), dim3(ST_BS), 0, eng->stream, (const double2 *)st.sums,
+                         npoin, nown, (double)st.nsamples, d);
+    });
   });
-  const int rc = download(eng, out, d, (size_t)want * sizeof(double));
-  (void)hipFree(d);
-  return rc;
 }
 
 extern "C" int hnumo_stats_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_stats_series: call hnumo_stats_begin first");
-  return series_read(eng, eng->stats.series, 0, 0, out, n, count, clear, "hnumo_stats_series", "2*nlayers");
+  const char *who = "hnumo_stats_series";
+  if (no_engine(eng) || not_begun(eng, eng->stats.on, who, "hnumo_stats_begin")) return HNUMO_ERR_INVALID;
+  return series_read(eng, eng->stats.series, 0, 0, out, n, count, clear, who, "2*nlayers");
 }
 
 // ------------------------------------------------------------------ vorticity products
@@ -336,27 +399,17 @@ static void vort_free(hnumo_engine *eng) {
 static size_t vort_nfields(const hnumo_engine *eng) { return 4 * (size_t)eng->npoin * eng->L; }
 
 extern "C" int hnumo_vort_begin(hnumo_engine *eng, const double *coriolis_df, int32_t every, int32_t series_capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (every < 0 || series_capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: every and series_capacity must be >= 0, got " +
-                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  const char *who = "hnumo_vort_begin";
+  if (no_engine(eng) || negative(eng, every, series_capacity, who, "every and series_capacity")) return HNUMO_ERR_INVALID;
   if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
     return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_begin: unsupported nlayers or ngl");
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
-  vort_free(eng);
+  if (int rc = drain_and_free(eng, vort_free)) return rc;
   auto &vt = eng->vort;
   const int rows = 3 * eng->L;
-  bool ok = alloc_doubles(&vt.fields, vort_nfields(eng)) && (!coriolis_df || alloc_doubles(&vt.f, (size_t)eng->npoin)) &&
-            (series_capacity == 0 || tree_alloc(vt.tree, rows, eng->nelem_owned)) &&
-            series_begin(eng, vt.series, rows, every, series_capacity, true) == hipSuccess;
-  if (ok && coriolis_df)
-    ok = hipMemcpy(vt.f, coriolis_df, (size_t)eng->npoin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    vort_free(eng);
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_vort_begin: device allocation or upload failed");
-  }
+  if (!alloc_doubles(&vt.fields, vort_nfields(eng)) || !upload_optional(&vt.f, coriolis_df, (size_t)eng->npoin) ||
+      (series_capacity > 0 && !tree_alloc(vt.tree, rows, eng->nelem_owned)) ||
+      series_begin(eng, vt.series, rows, every, series_capacity, true) != hipSuccess)
+    return begin_failed(eng, vort_free, "hnumo_vort_begin: device allocation or upload failed");
   // (the nodes of ghost elements are never written: they read 0)
   HIPCHK(hipMemsetAsync(vt.fields, 0, vort_nfields(eng) * sizeof(double), eng->stream));
   vt.on = true;
@@ -364,23 +417,16 @@ extern "C" int hnumo_vort_begin(hnumo_engine *eng, const double *coriolis_df, in
 }
 
 extern "C" int hnumo_vort_end(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->vort.on) return HNUMO_OK;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  vort_free(eng);
-  return HNUMO_OK;
+  return no_engine(eng) ? HNUMO_ERR_INVALID : observer_end(eng, eng->vort.on, vort_free);
 }
 
 // the fields of the state on the device into vort.fields, with `series` the next series entry too;
 // ordered after what is on the engine stream, no copy back
 static int vort_form(hnumo_engine *eng, bool series, const char *who) {
   auto &vt = eng->vort;
-  if (!vt.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_vort_begin first");
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  if (series && vt.series.cap == 0)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no series (hnumo_vort_begin with series_capacity = 0)");
+  if (not_begun(eng, vt.on, who, "hnumo_vort_begin") || no_state(eng, who) ||
+      (series && vt.series.cap == 0 && refused(eng, who, "no series (hnumo_vort_begin with series_capacity = 0)")))
+    return HNUMO_ERR_INVALID;
   if (series)
     if (int rc = series_full(eng, vt.series, who, "the series", "samples", "recorded")) return rc;
   const int ne = eng->nelem_owned, EPB = VT_BS / eng->P;
@@ -396,7 +442,7 @@ static int vort_form(hnumo_engine *eng, bool series, const char *who) {
     a.gravity = eng->p.gravity;
     a.npoin = eng->npoin;
     a.ne = ne;
-    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    const int nb = block_count(ne, EPB);
     with_ngl(eng->ngl, [&](auto ngl) {
       with_L(eng->L, [&](auto l) {
         constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
@@ -414,21 +460,19 @@ static int vort_form(hnumo_engine *eng, bool series, const char *who) {
 }
 
 extern "C" int hnumo_vort_record(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   return vort_form(eng, true, "hnumo_vort_record");
 }
 
 extern "C" int hnumo_vort_fields(hnumo_engine *eng, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->vort.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: call hnumo_vort_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: out is NULL");
+  const char *who = "hnumo_vort_fields";
+  if (no_engine(eng) || not_begun(eng, eng->vort.on, who, "hnumo_vort_begin") || null_arg(eng, out, who, "out") ||
+      wrong_n(eng, n, (int64_t)vort_nfields(eng), who, "4*npoin*nlayers"))
+    return HNUMO_ERR_INVALID;
   const size_t want = vort_nfields(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_fields: n must be 4*npoin*nlayers = " + std::to_string(want) +
-                                            ", got " + std::to_string(n));
   HIPCHK(hipSetDevice(eng->device));
-  if (int rc = vort_form(eng, false, "hnumo_vort_fields")) return rc;
+  if (int rc = vort_form(eng, false, who)) return rc;
   std::vector<double> raw(want);
   if (int rc = download(eng, raw.data(), eng->vort.fields, want * sizeof(double))) return rc;
   // planar [L][4][npoin] -> the caller's (4,npoin,L)
@@ -437,22 +481,22 @@ extern "C" int hnumo_vort_fields(hnumo_engine *eng, double *out, int64_t n) {
 }
 
 extern "C" int hnumo_vort_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->vort.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_vort_series: call hnumo_vort_begin first");
-  return series_read(eng, eng->vort.series, 0, 0, out, n, count, clear, "hnumo_vort_series", "3*nlayers");
+  const char *who = "hnumo_vort_series";
+  if (no_engine(eng) || not_begun(eng, eng->vort.on, who, "hnumo_vort_begin")) return HNUMO_ERR_INVALID;
+  return series_read(eng, eng->vort.series, 0, 0, out, n, count, clear, who, "3*nlayers");
 }
 
 // ------------------------------------------------------------------ eddy covariances
 // eng->cov: the caller's coriolis_df and zref (NULL: 0), the running sums [L][7][npoin] pairs, the
 // element partials [3L][ne] of the integrals with their tree and the integrals [3L]; nsamples: samples
-// taken since begin.  No series: `every` and `steps` alone say when a sample is due after a step
+// taken since begin.  The series has capacity 0: its every and steps alone say when a sample is due
 static void cov_free(hnumo_engine *eng) {
   auto &cv = eng->cov;
   dfree(cv.f, cv.zref, cv.sums, cv.integ);
   tree_free(cv.tree);
+  series_free(cv.series);
   cv.on = false;
-  cv.nsamples = cv.steps = 0;
-  cv.every = 0;
+  cv.nsamples = 0;
 }
 
 static size_t cov_nsums(const hnumo_engine *eng) { return CV_NSUM * (size_t)eng->npoin * eng->L; }
@@ -467,40 +511,28 @@ static void cov_with_L(int L, F &&f) {
 }
 
 extern "C" int hnumo_cov_begin(hnumo_engine *eng, const double *coriolis_df, const double *zref, int32_t every) {
-  if (!eng) return HNUMO_ERR_INVALID;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
   if (every < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_begin: every must be >= 0, got " + std::to_string(every));
   if (eng->L < 2 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
     return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_begin: unsupported nlayers or ngl (nlayers 2 or 3; ngl 3, 4, 5, 6 or 8), got " +
                                             std::to_string(eng->L) + ", " + std::to_string(eng->ngl));
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
-  cov_free(eng);
+  if (int rc = drain_and_free(eng, cov_free)) return rc;
   auto &cv = eng->cov;
   const size_t npoin = (size_t)eng->npoin;
-  bool ok = alloc_doubles(&cv.sums, cov_nsums(eng)) && alloc_doubles(&cv.integ, (size_t)CV_NINT * eng->L) &&
-            tree_alloc(cv.tree, CV_NINT * eng->L, eng->nelem_owned) && (!coriolis_df || alloc_doubles(&cv.f, npoin)) &&
-            (!zref || alloc_doubles(&cv.zref, npoin * eng->L));
-  if (ok && coriolis_df) ok = hipMemcpy(cv.f, coriolis_df, npoin * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && zref) ok = hipMemcpy(cv.zref, zref, npoin * eng->L * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    cov_free(eng);
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_cov_begin: device allocation or upload failed");
-  }
+  const int rows = CV_NINT * eng->L;
+  // (the tree serves hnumo_cov_integrals, whatever `every`; capacity 0 allocates no ring)
+  if (!alloc_doubles(&cv.sums, cov_nsums(eng)) || !alloc_doubles(&cv.integ, (size_t)rows) ||
+      !tree_alloc(cv.tree, rows, eng->nelem_owned) || !upload_optional(&cv.f, coriolis_df, npoin) ||
+      !upload_optional(&cv.zref, zref, npoin * eng->L) || series_begin(eng, cv.series, rows, every, 0, false) != hipSuccess)
+    return begin_failed(eng, cov_free, "hnumo_cov_begin: device allocation or upload failed");
   // (the nodes of ghost elements are never accumulated: their sums stay +0.0)
   HIPCHK(hipMemsetAsync(cv.sums, 0, cov_nsums(eng) * sizeof(double), eng->stream));
-  cv.every = every;
   cv.on = true;
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_cov_end(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->cov.on) return HNUMO_OK;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  cov_free(eng);
-  return HNUMO_OK;
+  return no_engine(eng) ? HNUMO_ERR_INVALID : observer_end(eng, eng->cov.on, cov_free);
 }
 
 static CovArgs cov_args(hnumo_engine *eng) {
@@ -525,13 +557,11 @@ static CovArgs cov_args(hnumo_engine *eng) {
 // one sample of the state on the device, ordered after what is on the engine stream; no copy back
 static int cov_sample(hnumo_engine *eng, const char *who) {
   auto &cv = eng->cov;
-  if (!cv.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_cov_begin first");
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (not_begun(eng, cv.on, who, "hnumo_cov_begin") || no_state(eng, who)) return HNUMO_ERR_INVALID;
   const int ne = eng->nelem_owned, EPB = CV_BS / eng->P;
   if (ne > 0) {
     const CovArgs a = cov_args(eng);
-    const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+    const int nb = block_count(ne, EPB);
     with_ngl(eng->ngl, [&](auto ngl) {
       cov_with_L(eng->L, [&](auto l) {
         constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
@@ -545,86 +575,54 @@ static int cov_sample(hnumo_engine *eng, const char *who) {
 }
 
 extern "C" int hnumo_cov_accumulate(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   return cov_sample(eng, "hnumo_cov_accumulate");
 }
 
-// the sums between the device layout [L][7][npoin][2] and the caller's (14,npoin,L)
+static_assert(CV_NSUM == 2 * CV_NPAIR, "the caller's (14,npoin,L) is the pairs' two halves side by side");
+
 extern "C" int hnumo_cov_sums(hnumo_engine *eng, double *out, int64_t n, int64_t *nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_sums: call hnumo_cov_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_sums: out is NULL");
-  const size_t want = cov_nsums(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_sums: n must be 14*npoin*nlayers = " + std::to_string(want) + ", got " +
-                                            std::to_string(n));
-  HIPCHK(hipSetDevice(eng->device));
-  std::vector<double> raw(want);
-  if (int rc = download(eng, raw.data(), eng->cov.sums, want * sizeof(double))) return rc;
-  for (int k = 0; k < eng->L; k++)
-    for (int p = 0; p < CV_NPAIR; p++)
-      for (size_t I = 0; I < npoin; I++)
-        for (int j = 0; j < 2; j++) out[CV_NSUM * (I + npoin * k) + 2 * p + j] = raw[2 * cv_pair(k, p, I, npoin) + j];
-  if (nsamples) *nsamples = eng->cov.nsamples;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
+  const auto &cv = eng->cov;
+  if (int rc = sums_read(eng, cv.on, cv.sums, CV_NPAIR, out, n, "hnumo_cov_sums", "hnumo_cov_begin", "14*npoin*nlayers")) return rc;
+  if (nsamples) *nsamples = cv.nsamples;
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_cov_set_sums(hnumo_engine *eng, const double *in, int64_t n, int64_t nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: call hnumo_cov_begin first");
-  if (!in) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: in is NULL");
-  const size_t want = cov_nsums(eng), npoin = (size_t)eng->npoin;
-  if (n != (int64_t)want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: n must be 14*npoin*nlayers = " + std::to_string(want) + ", got " +
-                                            std::to_string(n));
-  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_set_sums: nsamples must be >= 0");
-  HIPCHK(hipSetDevice(eng->device));
-  std::vector<double> raw(want);
-  for (int k = 0; k < eng->L; k++)
-    for (int p = 0; p < CV_NPAIR; p++)
-      for (size_t I = 0; I < npoin; I++)
-        for (int j = 0; j < 2; j++) raw[2 * cv_pair(k, p, I, npoin) + j] = in[CV_NSUM * (I + npoin * k) + 2 * p + j];
-  HIPCHK(hipMemcpyAsync(eng->cov.sums, raw.data(), want * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  eng->cov.nsamples = nsamples;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
+  auto &cv = eng->cov;
+  if (int rc = sums_write(eng, cv.on, cv.sums, CV_NPAIR, in, n, nsamples, "hnumo_cov_set_sums", "hnumo_cov_begin", "14*npoin*nlayers"))
+    return rc;
+  cv.nsamples = nsamples;
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_cov_fields(hnumo_engine *eng, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: call hnumo_cov_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: out is NULL");
+  const char *who = "hnumo_cov_fields";
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
+  const auto &cv = eng->cov;
   const int64_t want = CV_NFIELD * (int64_t)eng->npoin * eng->L;
-  if (n != want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: n must be 16*npoin*nlayers = " + std::to_string(want) + ", got " +
-                                            std::to_string(n));
-  if (eng->cov.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_fields: no samples yet");
-  HIPCHK(hipSetDevice(eng->device));
-  double *d = nullptr;
-  HIPCHK(hipMalloc((void **)&d, (size_t)want * sizeof(double)));
-  const size_t npoin = (size_t)eng->npoin, nown = (size_t)eng->nelem_owned * eng->P;
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>((npoin + CV_BS - 1) / CV_BS, 4096));
-  const double2 *s = (const double2 *)eng->cov.sums;
-  const double ns = (double)eng->cov.nsamples;
-  cov_with_L(eng->L, [&](auto l) {
-    hipLaunchKernelGGL(cov_fields_kernel<decltype(l)::value>, dim3(nb), dim3(CV_BS), 0, eng->stream, s, npoin, nown, ns, d);
+  if (not_begun(eng, cv.on, who, "hnumo_cov_begin") || null_arg(eng, out, who, "out") ||
+      wrong_n(eng, n, want, who, "16*npoin*nlayers") || no_samples(eng, cv.nsamples, who))
+    return HNUMO_ERR_INVALID;
+  return fields_of_sums(eng, want, CV_BS, out, [&](int nb, size_t npoin, size_t nown, double *d) {
+    cov_with_L(eng->L, [&](auto l) {
+      hipLaunchKernelGGL(cov_fields_kernel<decltype(l)::value>, dim3(nb), dim3(CV_BS), 0, eng->stream, (const double2 *)cv.sums,
+                         npoin, nown, (double)cv.nsamples, d);
+    });
   });
-  const int rc = download(eng, out, d, (size_t)want * sizeof(double));
-  (void)hipFree(d);
-  return rc;
 }
 
 // out(3,nlayers): the element partials, then the tree of the statistics' series
 extern "C" int hnumo_cov_integrals(hnumo_engine *eng, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->cov.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: call hnumo_cov_begin first");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: out is NULL");
+  const char *who = "hnumo_cov_integrals";
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
   const int rows = CV_NINT * eng->L;
-  if (n != rows)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: n must be 3*nlayers = " + std::to_string(rows) + ", got " +
-                                            std::to_string(n));
-  if (eng->cov.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_cov_integrals: no samples yet");
+  if (not_begun(eng, eng->cov.on, who, "hnumo_cov_begin") || null_arg(eng, out, who, "out") ||
+      wrong_n(eng, n, rows, who, "3*nlayers") || no_samples(eng, eng->cov.nsamples, who))
+    return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   const int ne = eng->nelem_owned, EPB = CV_BS / eng->P;
   if (ne == 0) {
@@ -632,7 +630,7 @@ extern "C" int hnumo_cov_integrals(hnumo_engine *eng, double *out, int64_t n) {
     return HNUMO_OK;
   }
   const CovArgs a = cov_args(eng);
-  const int nb = std::max(1, std::min((ne + EPB - 1) / EPB, 8192));
+  const int nb = block_count(ne, EPB);
   cov_with_L(eng->L, [&](auto l) {
     hipLaunchKernelGGL(cov_integrals_kernel<decltype(l)::value>, dim3(nb), dim3(CV_BS), 0, eng->stream, a);
   });
@@ -658,28 +656,18 @@ static size_t energy_nquad(const hnumo_engine *eng) { return 2 * (size_t)eng->np
 static size_t energy_nnodal(const hnumo_engine *eng) { return (size_t)eng->npoin * eng->L; }
 
 extern "C" int hnumo_energy_begin(hnumo_engine *eng, const double *zref, int32_t every, int32_t series_capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (every < 0 || series_capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_begin: every and series_capacity must be >= 0, got " +
-                                            std::to_string(every) + ", " + std::to_string(series_capacity));
+  const char *who = "hnumo_energy_begin";
+  if (no_engine(eng) || negative(eng, every, series_capacity, who, "every and series_capacity")) return HNUMO_ERR_INVALID;
   if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl) || eng->nq != 2 * eng->ngl - 1)
     return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_begin: unsupported nlayers or ngl (nlayers 1..3; ngl 3, 4, 5, 6 or 8), got " +
                                             std::to_string(eng->L) + ", " + std::to_string(eng->ngl));
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the old buffers)
-  energy_free(eng);
+  if (int rc = drain_and_free(eng, energy_free)) return rc;
   auto &en = eng->energy;
   const int rows = en_rows(eng->L);
-  bool ok = alloc_doubles(&en.sq, energy_nquad(eng)) && alloc_doubles(&en.sv, energy_nnodal(eng)) &&
-            (series_capacity == 0 || tree_alloc(en.tree, rows, eng->nelem_owned)) &&
-            (!zref || alloc_doubles(&en.zref, energy_nnodal(eng))) &&
-            series_begin(eng, en.series, rows, every, series_capacity, true) == hipSuccess;
-  if (ok && zref) ok = hipMemcpy(en.zref, zref, energy_nnodal(eng) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    (void)hipGetLastError();
-    energy_free(eng);
-    return fail(eng, HNUMO_ERR_DEVICE, "hnumo_energy_begin: device allocation or upload failed");
-  }
+  if (!alloc_doubles(&en.sq, energy_nquad(eng)) || !alloc_doubles(&en.sv, energy_nnodal(eng)) ||
+      (series_capacity > 0 && !tree_alloc(en.tree, rows, eng->nelem_owned)) || !upload_optional(&en.zref, zref, energy_nnodal(eng)) ||
+      series_begin(eng, en.series, rows, every, series_capacity, true) != hipSuccess)
+    return begin_failed(eng, energy_free, "hnumo_energy_begin: device allocation or upload failed");
   // (the points of ghost elements are never visited: their sums stay +0.0)
   HIPCHK(hipMemsetAsync(en.sq, 0, energy_nquad(eng) * sizeof(double), eng->stream));
   HIPCHK(hipMemsetAsync(en.sv, 0, energy_nnodal(eng) * sizeof(double), eng->stream));
@@ -688,12 +676,7 @@ extern "C" int hnumo_energy_begin(hnumo_engine *eng, const double *zref, int32_t
 }
 
 extern "C" int hnumo_energy_end(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->energy.on) return HNUMO_OK;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));
-  energy_free(eng);
-  return HNUMO_OK;
+  return no_engine(eng) ? HNUMO_ERR_INVALID : observer_end(eng, eng->energy.on, energy_free);
 }
 
 template <int NGL, int L, bool SERIES>
@@ -709,11 +692,9 @@ static void energy_launch(int botfr, int nb, hipStream_t st, const EnergyArgs &a
 // copy back
 static int energy_sample(hnumo_engine *eng, const char *who) {
   auto &en = eng->energy;
-  if (!en.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": call hnumo_energy_begin first");
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  if (eng->p.botfr < 0 || eng->p.botfr > 2)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": botfr must be 0, 1 or 2, got " + std::to_string(eng->p.botfr));
+  if (not_begun(eng, en.on, who, "hnumo_energy_begin") || no_state(eng, who) ||
+      ((eng->p.botfr < 0 || eng->p.botfr > 2) && refused(eng, who, "botfr must be 0, 1 or 2, got " + std::to_string(eng->p.botfr))))
+    return HNUMO_ERR_INVALID;
   const bool series = en.series.cap > 0;
   if (series)
     if (int rc = series_full(eng, en.series, who, "the series", "samples", "accumulated")) return rc;
@@ -736,7 +717,7 @@ static int energy_sample(hnumo_engine *eng, const char *who) {
     a.npoin = eng->npoin;
     a.npq = eng->npq;
     a.ne = ne;
-    const int nb = std::max(1, std::min((ne + EPG - 1) / EPG, 8192));
+    const int nb = block_count(ne, EPG);
     with_ngl(eng->ngl, [&](auto ngl) {
       with_L(eng->L, [&](auto l) {
         constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
@@ -755,37 +736,30 @@ static int energy_sample(hnumo_engine *eng, const char *who) {
 }
 
 extern "C" int hnumo_energy_sample(hnumo_engine *eng) {
-  if (!eng) return HNUMO_ERR_INVALID;
+  if (no_engine(eng)) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   return energy_sample(eng, "hnumo_energy_sample");
 }
 
 extern "C" int hnumo_energy_series(hnumo_engine *eng, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_series: call hnumo_energy_begin first");
-  if (eng->energy.series.cap == 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_series: no series (hnumo_energy_begin was given series_capacity = 0)");
-  return series_read(eng, eng->energy.series, 0, 0, out, n, count, clear, "hnumo_energy_series", "(3*nlayers+2)");
+  const char *who = "hnumo_energy_series";
+  if (no_engine(eng) || not_begun(eng, eng->energy.on, who, "hnumo_energy_begin") ||
+      (eng->energy.series.cap == 0 && refused(eng, who, "no series (hnumo_energy_begin was given series_capacity = 0)")))
+    return HNUMO_ERR_INVALID;
+  return series_read(eng, eng->energy.series, 0, 0, out, n, count, clear, who, "(3*nlayers+2)");
 }
 
-// 0, or the refusal of a wrong nq2 or nn
-static int energy_sizes(hnumo_engine *eng, const char *who, int64_t nq2, int64_t nn) {
-  const int64_t wq = (int64_t)energy_nquad(eng), wn = (int64_t)energy_nnodal(eng);
-  if (nq2 != wq)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": nq2 must be 2*npoin_q = " + std::to_string(wq) + ", got " +
-                                            std::to_string(nq2));
-  if (nn != wn)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": nn must be npoin*nlayers = " + std::to_string(wn) + ", got " +
-                                            std::to_string(nn));
-  return 0;
+// what hnumo_energy_sums, _set_sums and _means refuse alike: not begun, a NULL buffer, a wrong nq2 or nn
+static bool energy_sums_refused(hnumo_engine *eng, const void *quad2, int64_t nq2, const void *nodal, int64_t nn, const char *who) {
+  return no_engine(eng) || not_begun(eng, eng->energy.on, who, "hnumo_energy_begin") ||
+         ((!quad2 || !nodal) && refused(eng, who, "quad2 or nodal is NULL")) ||
+         wrong_n(eng, nq2, (int64_t)energy_nquad(eng), who, "2*npoin_q", "nq2") ||
+         wrong_n(eng, nn, (int64_t)energy_nnodal(eng), who, "npoin*nlayers", "nn");
 }
 
 // (the device layouts are the caller's: (2,npoin_q) and (npoin,nlayers))
 extern "C" int hnumo_energy_sums(hnumo_engine *eng, double *quad2, int64_t nq2, double *nodal, int64_t nn, int64_t *nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_sums: call hnumo_energy_begin first");
-  if (!quad2 || !nodal) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_sums: quad2 or nodal is NULL");
-  if (int rc = energy_sizes(eng, "hnumo_energy_sums", nq2, nn)) return rc;
+  if (energy_sums_refused(eng, quad2, nq2, nodal, nn, "hnumo_energy_sums")) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   HIPCHK(hipMemcpyAsync(quad2, eng->energy.sq, (size_t)nq2 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
   if (int rc = download(eng, nodal, eng->energy.sv, (size_t)nn * sizeof(double))) return rc;
@@ -795,11 +769,9 @@ extern "C" int hnumo_energy_sums(hnumo_engine *eng, double *quad2, int64_t nq2, 
 
 extern "C" int hnumo_energy_set_sums(hnumo_engine *eng, const double *quad2, int64_t nq2, const double *nodal, int64_t nn,
                                      int64_t nsamples) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_set_sums: call hnumo_energy_begin first");
-  if (!quad2 || !nodal) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_set_sums: quad2 or nodal is NULL");
-  if (int rc = energy_sizes(eng, "hnumo_energy_set_sums", nq2, nn)) return rc;
-  if (nsamples < 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_set_sums: nsamples must be >= 0");
+  const char *who = "hnumo_energy_set_sums";
+  if (energy_sums_refused(eng, quad2, nq2, nodal, nn, who) || (nsamples < 0 && refused(eng, who, "nsamples must be >= 0")))
+    return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   HIPCHK(hipMemcpyAsync(eng->energy.sq, quad2, (size_t)nq2 * sizeof(double), hipMemcpyHostToDevice, eng->stream));
   HIPCHK(hipMemcpyAsync(eng->energy.sv, nodal, (size_t)nn * sizeof(double), hipMemcpyHostToDevice, eng->stream));
@@ -810,11 +782,8 @@ extern "C" int hnumo_energy_set_sums(hnumo_engine *eng, const double *quad2, int
 
 // the sums divided by double(nsamples), on the host: S_W/N, S_D/N (2,npoin_q) and S_V/N (npoin,nlayers)
 extern "C" int hnumo_energy_means(hnumo_engine *eng, double *quad2, int64_t nq2, double *nodal, int64_t nn) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  if (!eng->energy.on) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_means: call hnumo_energy_begin first");
-  if (!quad2 || !nodal) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_means: quad2 or nodal is NULL");
-  if (int rc = energy_sizes(eng, "hnumo_energy_means", nq2, nn)) return rc;
-  if (eng->energy.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, "hnumo_energy_means: no samples yet");
+  const char *who = "hnumo_energy_means";
+  if (energy_sums_refused(eng, quad2, nq2, nodal, nn, who) || no_samples(eng, eng->energy.nsamples, who)) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   HIPCHK(hipMemcpyAsync(quad2, eng->energy.sq, (size_t)nq2 * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
   if (int rc = download(eng, nodal, eng->energy.sv, (size_t)nn * sizeof(double))) return rc;
@@ -845,7 +814,12 @@ static void regions_free(hnumo_engine *eng, int id) {
 }
 
 static RegionSet *regions_set(hnumo_engine *eng, int32_t id, const char *who) {
-  return set_by_id(eng, eng->regions, id, who, "region");
+  return no_engine(eng) ? nullptr : set_by_id(eng, eng->regions, id, who, "region");
+}
+
+static bool regions_no_series(hnumo_engine *eng, const RegionSet &s, int id, const char *who) {
+  return s.series.cap == 0 && refused(eng, who, "region set " + std::to_string(id) +
+                                                    " has no series (hnumo_regions_create was given series_capacity = 0)");
 }
 
 // the passes of the set's plan over `rows` rows of s.part into entry [rows][R]: one launch per pass,
@@ -865,12 +839,9 @@ static void regions_tree(hnumo_engine *eng, const RegionSet &s, int rows, double
 
 extern "C" int hnumo_regions_create(hnumo_engine *eng, const int32_t *region_of_elem, int64_t n, int32_t nregions, int32_t rows_mask,
                                     const double *coriolis_df, int32_t every, int32_t series_capacity, int32_t *id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   const char *who = "hnumo_regions_create";
-  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
-  if (every < 0 || series_capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": every and series_capacity must be >= 0, got " + std::to_string(every) +
-                                            ", " + std::to_string(series_capacity));
+  if (no_engine(eng) || null_arg(eng, id, who, "id") || negative(eng, every, series_capacity, who, "every and series_capacity"))
+    return HNUMO_ERR_INVALID;
   // (with_L and with_ngl dispatch these and no others; hnumo_vort_begin asks the same)
   if (eng->L < 1 || eng->L > MAXL || !sample_ngl_ok(eng->ngl))
     return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl (nlayers 1..3; ngl 3, 4, 5, 6 or 8), got " +
@@ -906,8 +877,7 @@ extern "C" int hnumo_regions_create(hnumo_engine *eng, const int32_t *region_of_
   if (ok) {
     // the areas: the members' sums of w_I*1.0 in node order into row 0 of part, then the same tree
     if (nmem > 0) {
-      const int EPB = RG_BS / eng->P;
-      const int nb = (int)std::max<size_t>(1, std::min<size_t>((nmem + EPB - 1) / EPB, 8192));
+      const int nb = block_count(nmem, RG_BS / eng->P);
       hipLaunchKernelGGL(region_area_kernel, dim3(nb), dim3(RG_BS), 0, eng->stream, eng->nstat + (size_t)NS_W * npoin, s.d_mem,
                          (int)nmem, eng->ngl, s.part);
     }
@@ -930,11 +900,7 @@ extern "C" int hnumo_regions_create(hnumo_engine *eng, const int32_t *region_of_
 
 // one sample of the set into its series, ordered after what is on the engine stream; no copy back
 static int regions_record(hnumo_engine *eng, RegionSet &s, int id, const char *who) {
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  if (s.series.cap == 0)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": region set " + std::to_string(id) +
-                                            " has no series (hnumo_regions_create was given series_capacity = 0)");
+  if (no_state(eng, who) || regions_no_series(eng, s, id, who)) return HNUMO_ERR_INVALID;
   if (int rc = series_full(eng, s.series, who, "the series of region set " + std::to_string(id), "samples", "recorded")) return rc;
   const int nmem = (int)s.plan.nmem(), EPB = RG_BS / eng->P;
   if (nmem > 0) {
@@ -949,7 +915,7 @@ static int regions_record(hnumo_engine *eng, RegionSet &s, int id, const char *w
     a.gravity = eng->p.gravity;
     a.npoin = eng->npoin;
     a.nmem = nmem;
-    const int nb = std::max(1, std::min((nmem + EPB - 1) / EPB, 8192));
+    const int nb = block_count(nmem, EPB);
     with_ngl(eng->ngl, [&](auto ngl) {
       with_L(eng->L, [&](auto l) {
         constexpr int NGL = decltype(ngl)::value, L = decltype(l)::value;
@@ -970,7 +936,6 @@ static int regions_record(hnumo_engine *eng, RegionSet &s, int id, const char *w
 }
 
 extern "C" int hnumo_regions_sample(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = regions_set(eng, id, "hnumo_regions_sample");
   if (!s) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
@@ -978,32 +943,23 @@ extern "C" int hnumo_regions_sample(hnumo_engine *eng, int32_t id) {
 }
 
 extern "C" int hnumo_regions_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = regions_set(eng, id, "hnumo_regions_series");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (s->series.cap == 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_regions_series: region set " + std::to_string(id) +
-                                            " has no series (hnumo_regions_create was given series_capacity = 0)");
-  return series_read(eng, s->series, s->V, (size_t)s->plan.R, out, n, count, clear, "hnumo_regions_series", "V*nregions");
+  const char *who = "hnumo_regions_series";
+  auto *s = regions_set(eng, id, who);
+  if (!s || regions_no_series(eng, *s, id, who)) return HNUMO_ERR_INVALID;
+  return series_read(eng, s->series, s->V, (size_t)s->plan.R, out, n, count, clear, who, "V*nregions");
 }
 
 extern "C" int hnumo_regions_area(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  const auto *s = regions_set(eng, id, "hnumo_regions_area");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_regions_area: out is NULL");
-  if (n != s->plan.R)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_regions_area: n must be the set's nregions = " + std::to_string(s->plan.R) + ", got " +
-                                            std::to_string(n));
+  const char *who = "hnumo_regions_area";
+  const auto *s = regions_set(eng, id, who);
+  if (!s || null_arg(eng, out, who, "out") || wrong_n(eng, n, s->plan.R, who, "the set's nregions")) return HNUMO_ERR_INVALID;
   std::memcpy(out, s->area.data(), (size_t)n * sizeof(double));
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_regions_destroy(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   if (!regions_set(eng, id, "hnumo_regions_destroy")) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the set's tables)
+  if (int rc = drain(eng)) return rc;  // (a sample in flight uses the set's tables)
   regions_free(eng, id);
   return HNUMO_OK;
 }
@@ -1021,7 +977,7 @@ static void sample_free(hnumo_engine *eng, int id) {
 }
 
 static SampleSet *sample_set(hnumo_engine *eng, int32_t id, const char *who) {
-  return set_by_id(eng, eng->samples, id, who, "sample");
+  return no_engine(eng) ? nullptr : set_by_id(eng, eng->samples, id, who, "sample");
 }
 
 // the located or given points of `pl` become a set: tables built and uploaded
@@ -1067,7 +1023,7 @@ static int sample_adopt(hnumo_engine *eng, SamplePlan &pl, const double *xgl, in
 }
 
 static int sample_create_checks(hnumo_engine *eng, int32_t source, const int32_t *id, const char *who) {
-  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
+  if (no_engine(eng) || null_arg(eng, id, who, "id")) return HNUMO_ERR_INVALID;
   if (source != HNUMO_SAMPLE_STATE && source != HNUMO_SAMPLE_STATS && source != HNUMO_SAMPLE_VORT && source != HNUMO_SAMPLE_COV)
     return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": source must be HNUMO_SAMPLE_STATE, HNUMO_SAMPLE_STATS, " +
                                             "HNUMO_SAMPLE_VORT or HNUMO_SAMPLE_COV, got " + std::to_string(source));
@@ -1082,7 +1038,6 @@ static int sample_create_checks(hnumo_engine *eng, int32_t source, const int32_t
 
 extern "C" int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
                                    int64_t M, int32_t source, int32_t *id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create")) return rc;
   SamplePlan pl;
   if (int rc = sample_locate(coord, ldc, xgl, eng->ngl, eng->nelem_owned, xy, M, pl, eng->err)) return rc;
@@ -1091,7 +1046,6 @@ extern "C" int hnumo_sample_create(hnumo_engine *eng, const double *coord, int32
 
 extern "C" int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, const int32_t *elem, const double *xi_eta,
                                        int64_t M, int32_t source, int32_t *id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   if (int rc = sample_create_checks(eng, source, id, "hnumo_sample_create_ref")) return rc;
   SamplePlan pl;
   if (int rc = sample_take_ref(xgl, eng->ngl, eng->nelem_owned, elem, xi_eta, M, pl, eng->err)) return rc;
@@ -1099,12 +1053,8 @@ extern "C" int hnumo_sample_create_ref(hnumo_engine *eng, const double *xgl, con
 }
 
 extern "C" int hnumo_sample_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
   const auto *s = sample_set(eng, id, "hnumo_sample_plan");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->plan.M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_plan: M must be the set's " + std::to_string(s->plan.M) + ", got " +
-                                            std::to_string(M));
+  if (!s || wrong_M(eng, M, s->plan.M, "hnumo_sample_plan")) return HNUMO_ERR_INVALID;
   if (elem) std::memcpy(elem, s->plan.elem.data(), (size_t)M * sizeof(int32_t));
   if (xi_eta) std::memcpy(xi_eta, s->plan.xi_eta.data(), 2 * (size_t)M * sizeof(double));
   return HNUMO_OK;
@@ -1112,8 +1062,7 @@ extern "C" int hnumo_sample_plan(hnumo_engine *eng, int32_t id, int32_t *elem, d
 
 // one sample of the set into `dst` [V][M] on the device, ordered after what is on the engine stream
 static int sample_now(hnumo_engine *eng, const SampleSet &s, double *dst, const char *who) {
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
+  if (no_state(eng, who)) return HNUMO_ERR_INVALID;
   if (s.source == HNUMO_SAMPLE_STATS) {
     if (!eng->stats.on) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set samples the flow statistics: call hnumo_stats_begin first");
     if (eng->stats.nsamples == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the flow statistics have no samples yet");
@@ -1174,15 +1123,13 @@ static int sample_now(hnumo_engine *eng, const SampleSet &s, double *dst, const 
 }
 
 extern "C" int hnumo_sample(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = sample_set(eng, id, "hnumo_sample");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: out is NULL");
+  const char *who = "hnumo_sample";
+  auto *s = sample_set(eng, id, who);
+  if (!s || null_arg(eng, out, who, "out")) return HNUMO_ERR_INVALID;
   const int64_t want = (int64_t)s->V * s->plan.M;
-  if (n != want)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample: n must be V*M = " + std::to_string(want) + ", got " + std::to_string(n));
+  if (wrong_n(eng, n, want, who, "V*M")) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
-  if (int rc = sample_now(eng, *s, s->d_out, "hnumo_sample")) return rc;
+  if (int rc = sample_now(eng, *s, s->d_out, who)) return rc;
   std::vector<double> raw((size_t)want);
   if (int rc = download(eng, raw.data(), s->d_out, (size_t)want * sizeof(double))) return rc;
   sample_transpose(raw.data(), s->V, (size_t)s->plan.M, 1, out);
@@ -1190,14 +1137,10 @@ extern "C" int hnumo_sample(hnumo_engine *eng, int32_t id, double *out, int64_t 
 }
 
 extern "C" int hnumo_sample_series_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = sample_set(eng, id, "hnumo_sample_series_begin");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (every < 0 || capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_sample_series_begin: every and capacity must be >= 0, got " +
-                                            std::to_string(every) + ", " + std::to_string(capacity));
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a recording in flight writes the old series)
+  const char *who = "hnumo_sample_series_begin";
+  auto *s = sample_set(eng, id, who);
+  if (!s || negative(eng, every, capacity, who, "every and capacity")) return HNUMO_ERR_INVALID;
+  if (int rc = drain(eng)) return rc;  // (a recording in flight writes the old series)
   // (no series: nothing to record into, so nothing is due after a step either)
   if (series_begin(eng, s->series, (size_t)s->V * (size_t)s->plan.M, capacity ? every : 0, capacity, false) != hipSuccess)
     return fail(eng, HNUMO_ERR_DEVICE, "hnumo_sample_series_begin: device allocation failed");
@@ -1212,7 +1155,6 @@ static int sample_record(hnumo_engine *eng, SampleSet &s, int id, const char *wh
 }
 
 extern "C" int hnumo_sample_record(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = sample_set(eng, id, "hnumo_sample_record");
   if (!s) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
@@ -1220,17 +1162,14 @@ extern "C" int hnumo_sample_record(hnumo_engine *eng, int32_t id) {
 }
 
 extern "C" int hnumo_sample_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = sample_set(eng, id, "hnumo_sample_series");
   if (!s) return HNUMO_ERR_INVALID;
   return series_read(eng, s->series, s->V, (size_t)s->plan.M, out, n, count, clear, "hnumo_sample_series", "V*M");
 }
 
 extern "C" int hnumo_sample_destroy(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   if (!sample_set(eng, id, "hnumo_sample_destroy")) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a sample in flight uses the set's tables)
+  if (int rc = drain(eng)) return rc;  // (a sample in flight uses the set's tables)
   sample_free(eng, id);
   return HNUMO_OK;
 }
@@ -1252,7 +1191,7 @@ static void floats_free(hnumo_engine *eng, int id) {
 }
 
 static FloatSet *floats_set(hnumo_engine *eng, int32_t id, const char *who) {
-  return set_by_id(eng, eng->floats, id, who, "float");
+  return no_engine(eng) ? nullptr : set_by_id(eng, eng->floats, id, who, "float");
 }
 
 // the plan's floats (sorted order) to the device
@@ -1268,9 +1207,8 @@ static bool floats_upload(FloatSet &s, const FloatPlan &pl) {
 
 extern "C" int hnumo_floats_create(hnumo_engine *eng, const double *coord, int32_t ldc, const double *xgl, const double *xy,
                                    const int32_t *layer, int64_t M, int32_t *id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   const char *who = "hnumo_floats_create";
-  if (!id) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": id is NULL");
+  if (no_engine(eng) || null_arg(eng, id, who, "id")) return HNUMO_ERR_INVALID;
   if (eng->L < 1 || eng->L > MAXL || !float_ngl_ok(eng->ngl))
     return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": unsupported nlayers or ngl");
   if (!eng->fl_nbr_err.empty()) return fail(eng, HNUMO_ERR_INVALID, eng->fl_nbr_err);
@@ -1316,15 +1254,11 @@ static bool floats_upload_iperm(hnumo_engine *eng, FloatSet &s) {
 }
 
 extern "C" int hnumo_floats_set(hnumo_engine *eng, int32_t id, const double *xy, const int32_t *layer, int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_set");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_set: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  if (!s || wrong_M(eng, M, s->M, "hnumo_floats_set")) return HNUMO_ERR_INVALID;
   FloatPlan pl;
   if (int rc = float_seed(s->geom, eng->L, xy, layer, M, pl, eng->err, "hnumo_floats_set")) return rc;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight writes the old floats)
+  if (int rc = drain(eng)) return rc;  // (an advance in flight writes the old floats)
   if (!floats_upload(*s, pl)) {
     (void)hipGetLastError();
     return fail(eng, HNUMO_ERR_DEVICE, "hnumo_floats_set: upload failed");
@@ -1416,9 +1350,7 @@ static FloatBox floats_box(const FloatSet &s, int which) {
 
 // one advance of the set on the state on the device now, and the record that is due after it
 static int floats_advance(hnumo_engine *eng, FloatSet &s, int id, double dt, const char *who) {
-  if (!eng->has_state)
-    return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  if (!float_finite(dt)) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": dt is not finite");
+  if (no_state(eng, who) || (!float_finite(dt) && refused(eng, who, "dt is not finite"))) return HNUMO_ERR_INVALID;
   FloatArgs a = floats_args(eng, s);
   a.dt = dt;
   if (s.mig) {
@@ -1450,7 +1382,6 @@ static int floats_advance(hnumo_engine *eng, FloatSet &s, int id, double dt, con
 }
 
 extern "C" int hnumo_floats_advance(hnumo_engine *eng, int32_t id, double dt) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_advance");
   if (!s) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
@@ -1458,16 +1389,13 @@ extern "C" int hnumo_floats_advance(hnumo_engine *eng, int32_t id, double dt) {
 }
 
 extern "C" int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, int32_t record_every, int32_t capacity) {
-  if (!eng) return HNUMO_ERR_INVALID;
-  auto *s = floats_set(eng, id, "hnumo_floats_begin");
+  const char *who = "hnumo_floats_begin";
+  auto *s = floats_set(eng, id, who);
   if (!s) return HNUMO_ERR_INVALID;
   if (every != 0 && every != 1)
     return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: every must be 0 or 1 (a float cannot skip steps), got " + std::to_string(every));
-  if (record_every < 0 || capacity < 0)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_begin: record_every and capacity must be >= 0, got " +
-                                            std::to_string(record_every) + ", " + std::to_string(capacity));
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a record in flight writes the old series)
+  if (negative(eng, record_every, capacity, who, "record_every and capacity")) return HNUMO_ERR_INVALID;
+  if (int rc = drain(eng)) return rc;  // (a record in flight writes the old series)
   s->every = 0;
   s->settle_due = false;
   // (record_every holds with capacity 0 too: the record that falls due is then refused as into a full series)
@@ -1478,7 +1406,6 @@ extern "C" int hnumo_floats_begin(hnumo_engine *eng, int32_t id, int32_t every, 
 }
 
 extern "C" int hnumo_floats_record(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_record");
   if (!s) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
@@ -1487,11 +1414,8 @@ extern "C" int hnumo_floats_record(hnumo_engine *eng, int32_t id) {
 
 extern "C" int hnumo_floats_get(hnumo_engine *eng, int32_t id, double *x, double *y, double *u, double *v, int32_t *elem,
                                 int32_t *status, int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_get");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_get: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  if (!s || wrong_M(eng, M, s->M, "hnumo_floats_get")) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   const size_t m = (size_t)M;
   std::vector<double> fd(4 * m);
@@ -1510,11 +1434,8 @@ extern "C" int hnumo_floats_get(hnumo_engine *eng, int32_t id, double *x, double
 }
 
 extern "C" int hnumo_floats_plan(hnumo_engine *eng, int32_t id, int32_t *elem, double *xi_eta, int64_t M) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_plan");
-  if (!s) return HNUMO_ERR_INVALID;
-  if (M != s->M)
-    return fail(eng, HNUMO_ERR_INVALID, "hnumo_floats_plan: M must be the set's " + std::to_string(s->M) + ", got " + std::to_string(M));
+  if (!s || wrong_M(eng, M, s->M, "hnumo_floats_plan")) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
   const size_t m = (size_t)M;
   std::vector<double> fd(2 * m);
@@ -1530,7 +1451,6 @@ extern "C" int hnumo_floats_plan(hnumo_engine *eng, int32_t id, int32_t *elem, d
 }
 
 extern "C" int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, int64_t n, int64_t *count, int32_t clear) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_series");
   if (!s) return HNUMO_ERR_INVALID;
   return series_read(eng, s->series, floats_nrows(*s), (size_t)s->M, out, n, count, clear, "hnumo_floats_series",
@@ -1538,7 +1458,6 @@ extern "C" int hnumo_floats_series(hnumo_engine *eng, int32_t id, double *out, i
 }
 
 extern "C" int hnumo_floats_sensors(hnumo_engine *eng, int32_t id, int32_t mask) {
-  if (!eng) return HNUMO_ERR_INVALID;
   const char *who = "hnumo_floats_sensors";
   auto *s = floats_set(eng, id, who);
   if (!s) return HNUMO_ERR_INVALID;
@@ -1552,15 +1471,13 @@ extern "C" int hnumo_floats_sensors(hnumo_engine *eng, int32_t id, int32_t mask)
                                             std::to_string(floats_nrows(*s)) + " rows, the mask asks for " +
                                             std::to_string(FL_NREC + fl_sense_rows(mask)) +
                                             ": call hnumo_floats_begin with capacity 0 first, then hnumo_floats_sensors, then hnumo_floats_begin");
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (a record in flight runs the old mask's kernel)
+  if (int rc = drain(eng)) return rc;  // (a record in flight runs the old mask's kernel)
   s->sensors = mask;
   if (s->series.cap == 0) s->series.width = (size_t)floats_nrows(*s) * (size_t)s->M;
   return HNUMO_OK;
 }
 
 extern "C" int hnumo_floats_sense_info(hnumo_engine *eng, int32_t id, int32_t *nrows, int32_t *K) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_sense_info");
   if (!s) return HNUMO_ERR_INVALID;
   if (nrows) *nrows = fl_sense_rows(s->sensors);
@@ -1577,15 +1494,13 @@ extern "C" int hnumo_floats_sense_info(hnumo_engine *eng, int32_t id, int32_t *n
 }
 
 extern "C" int hnumo_floats_sense(hnumo_engine *eng, int32_t id, double *out, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
   const char *who = "hnumo_floats_sense";
   auto *s = floats_set(eng, id, who);
   if (!s) return HNUMO_ERR_INVALID;
   const int S = fl_sense_rows(s->sensors);
   if (S == 0) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": float set " + std::to_string(id) + " has no sensors (hnumo_floats_sensors)");
-  if (!out) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": out is NULL");
   const int64_t want = (int64_t)S * s->M;
-  if (n != want) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": n must be S*M = " + std::to_string(want) + ", got " + std::to_string(n));
+  if (null_arg(eng, out, who, "out") || wrong_n(eng, n, want, who, "S*M")) return HNUMO_ERR_INVALID;
   if (int rc = floats_sense_refused(eng, *s, who)) return rc;
   HIPCHK(hipSetDevice(eng->device));
   // (sized for every sensor: the mask may change)
@@ -1601,10 +1516,8 @@ extern "C" int hnumo_floats_sense(hnumo_engine *eng, int32_t id, double *out, in
 }
 
 extern "C" int hnumo_floats_destroy(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   if (!floats_set(eng, id, "hnumo_floats_destroy")) return HNUMO_ERR_INVALID;
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (an advance in flight uses the set's tables)
+  if (int rc = drain(eng)) return rc;  // (an advance in flight uses the set's tables)
   floats_free(eng, id);
   return HNUMO_OK;
 }
@@ -1659,7 +1572,6 @@ static int floats_migrate(hnumo_engine *eng, int32_t id, int32_t on, double scal
 }
 
 extern "C" int hnumo_floats_migrate(hnumo_engine *eng, int32_t id, int32_t on, double coord_scale) {
-  if (!eng) return HNUMO_ERR_INVALID;
   return floats_migrate(eng, id, on, coord_scale, "hnumo_floats_migrate");
 }
 
@@ -1689,7 +1601,6 @@ static int floats_release(hnumo_engine *eng, FloatSet &s, const int32_t *idx, in
 }
 
 extern "C" int hnumo_floats_release(hnumo_engine *eng, int32_t id, const int32_t *idx, int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_release");
   if (!s) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
@@ -1780,8 +1691,7 @@ static int floats_group_advance(hnumo_engine **engines, int n, int32_t id, doubl
     bool any = false;
     for (int i = 0; i < n; i++) {
       hnumo_engine *eng = engines[i];
-      HIPCHK(hipSetDevice(eng->device));
-      HIPCHK(hipStreamSynchronize(eng->stream));
+      if (int rc = drain(eng)) return rc;
       auto &s = eng->floats[id];
       HIPCHK(hipMemcpy(&cnt[i], floats_box(s, s.parity).count, sizeof(int), hipMemcpyDeviceToHost));
       cnt[i] = std::min<int64_t>(std::max(cnt[i], 0), s.M);
@@ -1823,14 +1733,12 @@ static int floats_group_advance(hnumo_engine **engines, int n, int32_t id, doubl
 
 // ---- for a host that carries the flight records itself (one engine per process)
 extern "C" int hnumo_floats_outbox(hnumo_engine *eng, int32_t id, double *d, int32_t *i, int64_t cap, int64_t *count) {
-  if (!eng) return HNUMO_ERR_INVALID;
   const char *who = "hnumo_floats_outbox";
   auto *s = floats_set(eng, id, who);
   if (!s) return HNUMO_ERR_INVALID;
   if (!s->mig) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": the set does not migrate (hnumo_floats_migrate)");
-  if (!count) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": count is NULL");
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));
+  if (null_arg(eng, count, who, "count")) return HNUMO_ERR_INVALID;
+  if (int rc = drain(eng)) return rc;
   const FloatBox b = floats_box(*s, s->parity);
   int n = 0;
   HIPCHK(hipMemcpy(&n, b.count, sizeof(int), hipMemcpyDeviceToHost));
@@ -1863,7 +1771,6 @@ extern "C" int hnumo_floats_outbox(hnumo_engine *eng, int32_t id, double *d, int
 
 extern "C" int hnumo_floats_deliver(hnumo_engine *eng, int32_t id, int32_t src_rank, const double *d, const int32_t *i, int64_t cap,
                                     int64_t n) {
-  if (!eng) return HNUMO_ERR_INVALID;
   const char *who = "hnumo_floats_deliver";
   auto *s = floats_set(eng, id, who);
   if (!s) return HNUMO_ERR_INVALID;
@@ -1878,9 +1785,8 @@ extern "C" int hnumo_floats_deliver(hnumo_engine *eng, int32_t id, int32_t src_r
       return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": record " + std::to_string(t + 1) + " is no flight record (gid, layer, stage, hops or pos out of range)");
   }
   if (n == 0) return HNUMO_OK;
-  if (!eng->has_state) return fail(eng, HNUMO_ERR_INVALID, std::string(who) + ": no state on the device yet (run a step first)");
-  HIPCHK(hipSetDevice(eng->device));
-  HIPCHK(hipStreamSynchronize(eng->stream));  // (the arrivals of the last delivery read the inbox)
+  if (no_state(eng, who)) return HNUMO_ERR_INVALID;
+  if (int rc = drain(eng)) return rc;  // (the arrivals of the last delivery read the inbox)
   const FloatBox in = floats_box(*s, 2);
   const size_t M = (size_t)s->M;
   for (int v = 0; v < FL_FD; v++) HIPCHK(hipMemcpy(in.d + v * M, d + (size_t)v * cap, n * sizeof(double), hipMemcpyHostToDevice));
@@ -1893,7 +1799,6 @@ extern "C" int hnumo_floats_deliver(hnumo_engine *eng, int32_t id, int32_t src_r
 }
 
 extern "C" int hnumo_floats_settle(hnumo_engine *eng, int32_t id) {
-  if (!eng) return HNUMO_ERR_INVALID;
   auto *s = floats_set(eng, id, "hnumo_floats_settle");
   if (!s) return HNUMO_ERR_INVALID;
   HIPCHK(hipSetDevice(eng->device));
@@ -1916,7 +1821,7 @@ static int observers_after_step(hnumo_engine *eng) {
     run(stats_sample(eng, "flow statistics after the step (the step itself succeeded)"));
   if (eng->vort.on && eng->vort.series.cap > 0 && series_due(eng->vort.series))
     run(vort_form(eng, true, "vorticity series after the step (the step itself succeeded)"));
-  if (eng->cov.on && eng->cov.every > 0 && ++eng->cov.steps % eng->cov.every == 0)
+  if (eng->cov.on && series_due(eng->cov.series))
     run(cov_sample(eng, "eddy covariances after the step (the step itself succeeded)"));
   if (eng->energy.on && series_due(eng->energy.series))
     run(energy_sample(eng, "energy budget after the step (the step itself succeeded)"));
